@@ -10,6 +10,11 @@ of the step time), in GiB/s.  Workload (north star / BASELINE configs[3] per GPU
 
 Single GPU:  python bench.py [--steps K --warmup W]
 Multi GPU :  python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the steps and prints the result line.  --full adds what the
+headline figure does not need: the CPU baseline, the verification of every round trip, the parity
+of every member with the reference's digests, the lane-order guards, and the per-kernel / roofline
+figures of one extra profiled step.  --dump-outputs DIR writes what the last timed step computed.
 """
 import argparse
 import json
@@ -73,8 +78,14 @@ def parse():
     ap.add_argument("--n", type=int, default=10_000_000, help="values per GPU")
     ap.add_argument("--vlen", type=int, default=1024)
     ap.add_argument("--kind", type=int, default=0, help="0 JSON slices, 1 random alnum")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline, the round-trip verification, the reference-digest parity, the "
+                         "guard counters and one profiled step (per-kernel and roofline figures)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32 / "
+                         "float64; a fixed, seeded sample of the values, at most 64 MB in all)")
     ap.add_argument("--cpu-sample", type=int, default=300_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU baseline leg")
     ap.add_argument("--h2h", action="store_true", help="also time pinned H2D+kernel+D2H (host-to-host)")
     ap.add_argument("--h2h-chunk", type=int, default=0, help="values per chunk of the pipelined h2h leg (0 = n/16)")
     ap.add_argument("--mix", action="store_true",
@@ -156,6 +167,50 @@ def fullsize_parity(L, ctx, comp, coff, clen, n, vlen, kind, world, rank, sh):
     return {**out,
             "reference": f"tests/golden/{fname} (reference GzipCompressor::Compress, zlib "
                          f"{doc.get('zlib_version')})"}
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # of --dump-outputs' 64 MB limit
+DUMP_SEED = 0x5EED
+
+
+def dump_sample(n, row_elems):
+    """Indices of the values --dump-outputs writes: all n if they fit the budget as float32, else a sorted
+    sample drawn without replacement by a fixed seed (the same for every run with the same arguments)."""
+    import numpy as np
+    s = max(1, DUMP_BUDGET_BYTES // (4 * row_elems))
+    if n <= s:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=s, replace=False)).astype(np.int64)
+
+
+def dump_outputs(path, comp, coff, clen, crc, back, off, blen, brc, n, vlen, cstride, rank, world):
+    """--dump-outputs: what compress_device and decompress_device handed the caller in the last timed step.
+    Per sampled value: its member (slot bytes past the member's length are scratch and written as 0), the
+    member's length and return code, the decompressed bytes, their length and return code.  `totals` covers
+    every value of the batch: sum of member lengths, non-zero compress codes, sum of decompressed lengths,
+    non-zero decompress codes."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    idx_h = dump_sample(n, cstride + vlen + 8)
+    idx = torch.from_numpy(idx_h).to(comp.device)
+    col = torch.arange(cstride, device=comp.device)[None, :]
+    members = comp[coff[idx][:, None] + col]
+    members = torch.where(col < clen[idx][:, None], members, torch.zeros_like(members))
+    values = back[off[idx][:, None] + torch.arange(vlen, device=comp.device)[None, :]]
+    totals = torch.stack([clen.to(torch.int64).sum(), (crc != 0).sum(), blen.to(torch.int64).sum(),
+                          (brc != 0).sum()]).to(torch.float64)
+    arrays = {"sample_index": idx_h.astype(np.float64), "totals": totals.cpu().numpy(),
+              "compressed": members.to(torch.float32).cpu().numpy(),
+              "compressed_len": clen[idx].to(torch.float32).cpu().numpy(),
+              "compress_rc": crc[idx].to(torch.float32).cpu().numpy(),
+              "decompressed": values.to(torch.float32).cpu().numpy(),
+              "decompressed_len": blen[idx].to(torch.float32).cpu().numpy(),
+              "decompress_rc": brc[idx].to(torch.float32).cpu().numpy()}
+    tag = f".rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}{tag}.npy"), a)
+    return sum(a.nbytes for a in arrays.values())
 
 
 def cpu_baseline(corpus, args, index0):
@@ -523,9 +578,9 @@ def main():
         corpus_b = corpus_b * (vlen // len(corpus_b) + 2)
     seed = 0x5EED if args.kind == 0 else 0xA1B2
 
-    # ---- CPU baseline first (host idle), rank 0 at N=1 only ------------------------------
+    # ---- --full: CPU baseline first (host idle), rank 0 at N=1 only ----------------------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(corpus_b, args, 0)
 
     ctx = pmc_codec.Context(local)
@@ -599,16 +654,23 @@ def main():
     tc = sum(e[0].elapsed_time(e[1]) for e in evs) / args.steps / 1e3  # s per compress launch set
     td = sum(e[1].elapsed_time(e[2]) for e in evs) / args.steps / 1e3
 
-    # ---- verification of the last step (device-side compare, all values) ----------------
-    mism = torch.zeros(1, dtype=torch.int32, device=dev)
-    assert L.pmc_compare_values(src.data_ptr(), off.data_ptr(), back.data_ptr(), off.data_ptr(), lens.data_ptr(),
-                                blen.data_ptr(), n, mism.data_ptr(), sh) == 0
-    torch.cuda.synchronize()
-    bad = int(mism.item()) + int((crc != 0).sum().item()) + int((brc != 0).sum().item())
-    comp_bytes = int(clen.to(torch.int64).sum().item())
-    parity = fullsize_parity(L, ctx, comp, coff, clen, n, vlen, args.kind, sel_world, sel_rank, sh)
-    if args.emulate and parity is not None:
-        parity["emulated"] = f"rank {sel_rank} of {sel_world}"
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, comp, coff, clen, crc, back, off, blen, brc, n, vlen, cstride,
+                              rank, world)
+
+    bad, comp_bytes, parity = 0, 0, None
+    if args.full:
+        # ---- verification of the last step (device-side compare, all values) ----------------
+        mism = torch.zeros(1, dtype=torch.int32, device=dev)
+        assert L.pmc_compare_values(src.data_ptr(), off.data_ptr(), back.data_ptr(), off.data_ptr(),
+                                    lens.data_ptr(), blen.data_ptr(), n, mism.data_ptr(), sh) == 0
+        torch.cuda.synchronize()
+        bad = int(mism.item()) + int((crc != 0).sum().item()) + int((brc != 0).sum().item())
+        comp_bytes = int(clen.to(torch.int64).sum().item())
+        parity = fullsize_parity(L, ctx, comp, coff, clen, n, vlen, args.kind, sel_world, sel_rank, sh)
+        if args.emulate and parity is not None:
+            parity["emulated"] = f"rank {sel_rank} of {sel_world}"
 
     (t_step_s, tc_max, td_max), (total_bytes, total_comp, total_bad, p_match, p_checked) = reduce_over_ranks(
         [wall / args.steps, tc, td], [float(n * vlen), float(comp_bytes), float(bad),
@@ -619,14 +681,16 @@ def main():
                   "ranks_matching": int(p_match), "members": n * world, "method": parity["method"],
                   "reference": parity["reference"]}
 
-    # ---- lane-order guards (DESIGN §4 Guards): over the run, no value may have been rerouted -------
-    guards = ctx.guard_counts()
+    guards = ktimes = None
+    if args.full:
+        # ---- lane-order guards (DESIGN §4 Guards): over the run, no value may have been rerouted -------
+        guards = ctx.guard_counts()
 
-    # ---- per-kernel launch times of one more step (HIP events around every launch) -----------
-    ctx.profile(True)
-    step()
-    ktimes = ctx.kernel_times()
-    ctx.profile(False)
+        # ---- per-kernel launch times of one more step (HIP events around every launch) -----------
+        ctx.profile(True)
+        step()
+        ktimes = ctx.kernel_times()
+        ctx.profile(False)
 
     h2h = None
     if args.h2h and world == 1:
@@ -635,50 +699,8 @@ def main():
 
     if rank == 0:
         gib = total_bytes / 2 ** 30
-        # roofline of the dominant kernel: algorithmic bytes per launch
-        alg_c = n * (vlen + META_BYTES) + comp_bytes
-        alg_d = comp_bytes + n * (vlen + META_BYTES)
-        # dominant compress kernel: the one with the largest summed launch time in the profiled step
-        ckinds = [k for k in ktimes if k.startswith("deflate")]
-        dom = max(ckinds, key=lambda k: ktimes[k][0])
-        dom_ms, dom_launches = ktimes[dom]
-        avg_launch_s = dom_ms / dom_launches / 1e3
-        alg_launch = alg_c / dom_launches  # mean over the launches (chunks of the batch; the last one is shorter)
-        achieved = alg_launch / avg_launch_s / 1e9
-        # measured HBM bytes per launch of that kernel and its issue counters (scripts/pmc_traffic.py),
-        # quoted only when measured on these kernel sources and this workload
-        traffic, issue, tsrc = None, None, None
-        if os.path.exists(args.traffic):
-            try:
-                with open(args.traffic) as f:
-                    tj = json.load(f)
-                if (tj.get("n") == n and tj.get("vlen") == vlen and tj.get("kind") == args.kind
-                        and tj.get("source_id") == pmc_codec.source_id()):
-                    # (a templated kernel is listed per instance, "name<1024u>": the one this workload ran)
-                    kn, ks = pmc_codec.KERNEL_NAMES[dom], tj.get("kernels", {})
-                    inst = [k for k in ks if k == kn or k.startswith(kn + "<")]
-                    kj = max((ks[k] for k in inst), key=lambda e: e.get("launches", 0), default={})
-                    traffic = kj.get("hbm_bytes_per_launch")
-                    issue = kj.get("issue")
-                    tsrc = os.path.relpath(args.traffic, ROOT)
-            except (OSError, ValueError):
-                traffic = None
-        # issue floors of the dominant kernel from its counters (when measured on these sources): a wave64
-        # VALU instruction occupies its SIMD 2 cycles (4 SIMDs per CU), a scalar instruction the CU's one
-        # scalar unit 1 cycle; the clock is the measured GRBM_GUI_ACTIVE / 8 XCDs over the launch time
-        floors = None
-        if issue and issue.get("counters_per_launch"):
-            cp = issue["counters_per_launch"]
-            per_launch_vals = n / dom_launches
-            clk_hz = cp["GRBM_GUI_ACTIVE"] / 8.0 / avg_launch_s
-            cus = 256
-            floors = {"valu_per_value": cp["SQ_INSTS_VALU"] / per_launch_vals,
-                      "salu_per_value": cp["SQ_INSTS_SALU"] / per_launch_vals,
-                      "clock_ghz": clk_hz / 1e9,
-                      "valu_floor_ms": cp["SQ_INSTS_VALU"] * 2.0 / (4 * cus) / clk_hz * 1e3,
-                      "salu_floor_ms": cp["SQ_INSTS_SALU"] / cus / clk_hz * 1e3,
-                      "note": "per launch; VALU: 2 cycles per wave64 instruction on each of 4 SIMDs per CU, "
-                              "SALU: one scalar unit per CU"}
+        checked = ("every member checked against the reference by a (length, CRC-32) digest (fullsize_parity)"
+                   if args.full else "outputs not checked in this run (--full checks every member)")
         out = {
             "metric": METRIC, "value": gib / t_step_s, "unit": "GiB/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": t_step_s * 1e3, "higher_is_better": True, "scaling": "weak",
@@ -686,44 +708,101 @@ def main():
             "data": "synthetic: JSON slices of the reference's tests/data corpus (SURVEY.md §8d generator, "
                     f"seed {seed:#x})" if args.kind == 0 else "synthetic: random [A-Za-z0-9]",
             "config": {"workload": f"{n} x {vlen} B values per GPU ({'JSON-slice' if args.kind == 0 else 'alnum'}), "
-                                   "batched gzip level-9 compress + decompress, device-resident; every member "
-                                   "checked against the reference by a (length, CRC-32) digest (fullsize_parity)",
+                                   "batched gzip level-9 compress + decompress, device-resident; " + checked,
                        "values_per_gpu": n, "value_bytes": vlen, "total_values": n * world,
                        "partition": "MurmurHash3_x64_128('key'+i)[0] % 128 % n_gpus (NUM_SHARDS=128)",
                        "parallelism": f"shard-partitioned x{world}, no collective"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": tsrc,
-                         "issue": issue, "issue_floors": floors,
-                         # the whole step (compress + decompress) against the same peak
-                         "path": {"alg_bytes_per_step": alg_c + alg_d,
-                                  "achieved": (alg_c + alg_d) / (tc + td) / 1e9,
-                                  "frac": (alg_c + alg_d) / (tc + td) / 1e9 / HBM_PEAK_GBS},
-                         "kernel": pmc_codec.KERNEL_NAMES[dom],
-                         "alg_bytes_per_launch": alg_launch, "avg_launch_ms": avg_launch_s * 1e3,
-                         "launches_per_step": dom_launches,
-                         "kernel_ms_per_step": {pmc_codec.KERNEL_NAMES.get(k, k): round(v[0], 3)
-                                                for k, v in ktimes.items()}},
-            "cpu_baseline": cpu,
             "compress_gib_s": gib / world / tc_max, "decompress_gib_s": gib / world / td_max,
-            "decompress_roofline_frac": alg_d / td / 1e9 / HBM_PEAK_GBS,
-            "ratio": total_comp / total_bytes, "verified_values": int(total_bytes // vlen),
-            "mismatches": int(total_bad),
-            "fullsize_parity": parity,
-            "guard_counts": guards,
         }
+        if args.full:
+            alg_d = comp_bytes + n * (vlen + META_BYTES)
+            out.update({
+                "roofline": roofline(args, n, vlen, comp_bytes, ktimes, tc, td),
+                "cpu_baseline": cpu,
+                "decompress_roofline_frac": alg_d / td / 1e9 / HBM_PEAK_GBS,
+                "ratio": total_comp / total_bytes, "verified_values": int(total_bytes // vlen),
+                "mismatches": int(total_bad),
+                "fullsize_parity": parity,
+                "guard_counts": guards,
+            })
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "bytes": dumped}
         if h2h:
             out["host_to_host"] = h2h
         if landing:
             out["landing"] = landing
             out["config"]["parallelism"] = f"shard-partitioned x{world}; batch landed on rank 0, one all-to-all"
         print(json.dumps(out), flush=True)
-        # a guard that fired means values silently took the slow retry kernel: fail the run loudly (the
-        # line above still records the counts); large periodic values may legitimately take the stitch's
-        # fallback (guard_counts.retry), small ones never
-        assert guards["sort"] == 0 and guards["codes"] == 0 and guards["probe"] == 0, guards
-        assert vlen > 31808 or guards["retry"] == 0, guards
+        if args.full:
+            # a guard that fired means values silently took the slow retry kernel: fail the run loudly (the
+            # line above still records the counts); large periodic values may legitimately take the stitch's
+            # fallback (guard_counts.retry), small ones never
+            assert guards["sort"] == 0 and guards["codes"] == 0 and guards["probe"] == 0, guards
+            assert vlen > 31808 or guards["retry"] == 0, guards
     if distributed:
         dist.destroy_process_group()
+
+
+def roofline(args, n, vlen, comp_bytes, ktimes, tc, td):
+    """--full: the roofline object of the result line, from the profiled step's per-kernel times (ktimes), the
+    timed steps' compress / decompress seconds (tc, td) and the measured counters of --traffic."""
+    import pmc_codec
+    # roofline of the dominant kernel: algorithmic bytes per launch (SURVEY.md §8d)
+    alg_c = n * (vlen + META_BYTES) + comp_bytes
+    alg_d = comp_bytes + n * (vlen + META_BYTES)
+    # dominant compress kernel: the one with the largest summed launch time in the profiled step
+    ckinds = [k for k in ktimes if k.startswith("deflate")]
+    dom = max(ckinds, key=lambda k: ktimes[k][0])
+    dom_ms, dom_launches = ktimes[dom]
+    avg_launch_s = dom_ms / dom_launches / 1e3
+    alg_launch = alg_c / dom_launches  # mean over the launches (chunks of the batch; the last one is shorter)
+    achieved = alg_launch / avg_launch_s / 1e9
+    # measured HBM bytes per launch of that kernel and its issue counters (scripts/pmc_traffic.py),
+    # quoted only when measured on these kernel sources and this workload
+    traffic, issue, tsrc = None, None, None
+    if os.path.exists(args.traffic):
+        try:
+            with open(args.traffic) as f:
+                tj = json.load(f)
+            if (tj.get("n") == n and tj.get("vlen") == vlen and tj.get("kind") == args.kind
+                    and tj.get("source_id") == pmc_codec.source_id()):
+                # (a templated kernel is listed per instance, "name<1024u>": the one this workload ran)
+                kn, ks = pmc_codec.KERNEL_NAMES[dom], tj.get("kernels", {})
+                inst = [k for k in ks if k == kn or k.startswith(kn + "<")]
+                kj = max((ks[k] for k in inst), key=lambda e: e.get("launches", 0), default={})
+                traffic = kj.get("hbm_bytes_per_launch")
+                issue = kj.get("issue")
+                tsrc = os.path.relpath(args.traffic, ROOT)
+        except (OSError, ValueError):
+            traffic = None
+    # issue floors of the dominant kernel from its counters (when measured on these sources): a wave64
+    # VALU instruction occupies its SIMD 2 cycles (4 SIMDs per CU), a scalar instruction the CU's one
+    # scalar unit 1 cycle; the clock is the measured GRBM_GUI_ACTIVE / 8 XCDs over the launch time
+    floors = None
+    if issue and issue.get("counters_per_launch"):
+        cp = issue["counters_per_launch"]
+        per_launch_vals = n / dom_launches
+        clk_hz = cp["GRBM_GUI_ACTIVE"] / 8.0 / avg_launch_s
+        cus = 256
+        floors = {"valu_per_value": cp["SQ_INSTS_VALU"] / per_launch_vals,
+                  "salu_per_value": cp["SQ_INSTS_SALU"] / per_launch_vals,
+                  "clock_ghz": clk_hz / 1e9,
+                  "valu_floor_ms": cp["SQ_INSTS_VALU"] * 2.0 / (4 * cus) / clk_hz * 1e3,
+                  "salu_floor_ms": cp["SQ_INSTS_SALU"] / cus / clk_hz * 1e3,
+                  "note": "per launch; VALU: 2 cycles per wave64 instruction on each of 4 SIMDs per CU, "
+                          "SALU: one scalar unit per CU"}
+    return {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": tsrc,
+            "issue": issue, "issue_floors": floors,
+            # the whole step (compress + decompress) against the same peak
+            "path": {"alg_bytes_per_step": alg_c + alg_d,
+                     "achieved": (alg_c + alg_d) / (tc + td) / 1e9,
+                     "frac": (alg_c + alg_d) / (tc + td) / 1e9 / HBM_PEAK_GBS},
+            "kernel": pmc_codec.KERNEL_NAMES[dom],
+            "alg_bytes_per_launch": alg_launch, "avg_launch_ms": avg_launch_s * 1e3,
+            "launches_per_step": dom_launches,
+            "kernel_ms_per_step": {pmc_codec.KERNEL_NAMES.get(k, k): round(v[0], 3)
+                                   for k, v in ktimes.items()}}
 
 
 def scatter_landing(L, args, route, corpus, corpus_len, seed, world, rank, n, vlen, dev, sh):

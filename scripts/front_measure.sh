@@ -10,5 +10,5 @@ PMC_LIB=libpmc_codec_stamps.so timeout -k 10 240 python -u scripts/stamps.py 102
     > "$OUT/stamps.txt" 2>&1 || exit $?
 TAG=${TAG:-front}/fcost N=200000 bash scripts/front_cost.sh > "$OUT/front_cost.txt" 2>&1 || exit $?
 TAG=${TAG:-front}/flds N=200000 bash scripts/front_lds.sh > "$OUT/front_lds.txt" 2>&1 || exit $?
-timeout -k 10 300 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
+timeout -k 10 300 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
 tail -n 1 "$OUT/bench.json"

@@ -7,6 +7,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 TAG=${TAG:-abab}
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the per-kernel figures read below are --full's
 for r in 1 2; do
   timeout -k 10 300 python bench.py --no-cpu-baseline ${BENCH_ARGS:-} > gpurun_out/${TAG}_A$r.json 2> gpurun_out/${TAG}_A$r.err || exit $?
   env ${ENV_B:-} PMC_LIB=${ALT:-libpmc_codec_alt.so} timeout -k 10 300 python bench.py --no-cpu-baseline ${BENCH_ARGS:-} > gpurun_out/${TAG}_B$r.json 2> gpurun_out/${TAG}_B$r.err || exit $?

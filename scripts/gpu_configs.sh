@@ -8,6 +8,7 @@ T=${TAG:-cfg}
 mkdir -p gpurun_out/$T
 run() { # name, args...
   local name=$1; shift
+  set -- --full "$@"  # the digest match (fullsize_parity) is --full's
   timeout -k 10 ${TLIM:-300} python bench.py --no-cpu-baseline "$@" > gpurun_out/$T/$name.json 2> gpurun_out/$T/$name.err || return $?
   python3 scripts/bench_line.py gpurun_out/$T/$name.json $name
 }

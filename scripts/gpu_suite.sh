@@ -10,5 +10,5 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 240 --timeout
 tail -3 $O/pytest_gpu.txt; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1 || exit $?
 tail -1 $O/smoke.txt
-timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err || exit $?
+timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err || exit $?
 python3 scripts/bench_line.py $O/bench.json default

@@ -7,6 +7,7 @@ export TMPDIR=/tmp
 T=${TAG:-variants}
 mkdir -p gpurun_out/$T
 LIBS=${LIBS:-libpmc_codec.so libpmc_codec_alt.so}
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # parity and per-kernel figures are --full's
 for L in $LIBS; do
   PMC_LIB=$L timeout -k 10 400 python -u -m pytest tests/test_gpu_codec.py -x -q -m gpu -k "golden or ragged" --timeout 240 --timeout-method thread > gpurun_out/$T/pytest_$L.txt 2>&1; rc=$?
   echo "$L parity: $(tail -1 gpurun_out/$T/pytest_$L.txt)"; [ $rc -eq 0 ] || exit $rc

@@ -8,7 +8,7 @@ TAG=${TAG:-pmc}
 N=${N:-1000000}
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
-BENCH="bench.py --n $N --steps 1 --warmup 1 --no-cpu-baseline"
+BENCH="bench.py --full --n $N --steps 1 --warmup 1 --no-cpu-baseline"
 timeout -k 10 120 rocprofv3 -L > "$OUT/counters.txt" 2>&1 || true
 pass() {
     local name=$1; shift

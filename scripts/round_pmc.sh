@@ -9,7 +9,7 @@ ROUND=${ROUND:-r02}
 TAG=${TAG:-pmc}
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT" "profiles/$ROUND"
-BENCH="bench.py --steps 1 --warmup 0 --no-cpu-baseline"
+BENCH="bench.py --full --steps 1 --warmup 0 --no-cpu-baseline"
 pass() {
     local name=$1; shift
     timeout -k 10 300 rocprofv3 --kernel-trace --pmc "$@" -d "$OUT/$name" -o run --output-format csv \
