@@ -13,7 +13,8 @@
  * in the signatures (streams are passed as void* = hipStream_t).
  *
  * Output bytes are bit-identical to the reference Compress (zlib 1.2.11, level 9,
- * windowBits 15+16, memLevel 8, default strategy) on the same input bytes.
+ * windowBits 15+16, memLevel 8, default strategy) on the same input bytes -- at the default
+ * level.  A caller may trade that for compress speed: see "compression level" below.
  *
  * Return codes mirror the reference (gzip_compressor.hpp:10-12) and zlib:
  */
@@ -41,8 +42,36 @@ extern "C" {
  * note on streams below. */
 typedef struct pmc_ctx pmc_ctx;
 
-/* Create a context on HIP device `device` (gfx950).  Returns PMC_OK or PMC_E_NO_DEVICE. */
+/* Create a context on HIP device `device` (gfx950).  Returns PMC_OK or PMC_E_NO_DEVICE; PMC_E_ARG
+ * (and a pmc_last_error text) when the environment variable PMC_LEVEL holds something else than
+ * fast / 1 / exact / 9 (see the levels below). */
 int pmc_ctx_create(int device, pmc_ctx **out);
+
+/* ---- compression level ------------------------------------------------------------------
+ * A context compresses at one of two levels:
+ *   PMC_LEVEL_EXACT (9, the default): the reference's bytes, as stated above.
+ *   PMC_LEVEL_FAST (1): every value of at most 16382 bytes is parsed by a GPU-shaped match finder
+ *     (two hash candidates per position, matches found up to 32 bytes and extended when taken, a
+ *     one-step lazy rule; DESIGN.md §4 "Front, fast level") instead of zlib's level-9 deflate_slow.
+ *     The contract at this level: the output is one valid gzip member (one DEFLATE block, at most
+ *     pmc_gzip_bound(len) bytes, header byte 8 = 4) that the reference's Decompress -- any inflate
+ *     -- decodes to the input.  It is NOT the reference's bytes.  It is deterministic per value: the
+ *     same value gives the same member through every entry point, batch size and batch position
+ *     (a fast-level compress never takes the one-kernel latency path).  Values above 16382 bytes take
+ *     the exact paths unchanged and come out as the reference's bytes (header byte 8 = 2); so does a
+ *     value whose hash sort fails the lane-order guard (pmc_ctx_guard_counts counts[0]; never seen on
+ *     gfx950), which the retry kernel redoes at level 9.  Decompress is the same at both levels.
+ * pmc_ctx_set_level takes effect for the calls issued after it returns; stores and slabs compress
+ * through their context and follow it.  Any other level, or a NULL context, gives PMC_E_ARG (no device
+ * is touched); so does PMC_LEVEL_FAST on a context whose create-time lane-order probe failed (its
+ * level stays 9).  pmc_group_set_level sets every member context, or none.
+ * The environment variable PMC_LEVEL (fast / 1, exact / 9) sets the initial level of every context
+ * created afterwards, the default context -- hence the drop-in GzipCompressor and the servers --
+ * included; unset means exact. */
+#define PMC_LEVEL_EXACT 9
+#define PMC_LEVEL_FAST 1
+int pmc_ctx_set_level(pmc_ctx *ctx, int level);
+int pmc_ctx_get_level(pmc_ctx *ctx, int *level);
 void pmc_ctx_destroy(pmc_ctx *ctx);
 /* Default context (device 0), created on first use; used by the drop-in. */
 pmc_ctx *pmc_default_ctx(void);
@@ -238,6 +267,8 @@ uint64_t pmc_key_hash(const void *key, size_t len);
 int pmc_group_create(const int *devices, int n, pmc_group **out);
 void pmc_group_destroy(pmc_group *g);
 int pmc_group_size(pmc_group *g);
+/* pmc_ctx_set_level on every member context (all or none). */
+int pmc_group_set_level(pmc_group *g, int level);
 /* member[i] = (key_hash[i] % num_shards) % pmc_group_size(g) */
 int pmc_group_route(pmc_group *g, const uint64_t *key_hash, uint32_t num_shards, uint32_t n, uint32_t *member);
 int pmc_group_compress_batch(pmc_group *g, const uint8_t *src, const uint64_t *src_off, const uint32_t *src_len,

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
@@ -184,6 +185,8 @@ struct pmc_ctx {
     DevBuf guard;
     DevBuf rlist;                // compress: the per-call retry list (DeflateArgs::rlist)
     bool lane_order_ok = true;
+    // compression level of the calls issued from now on (pmc_ctx_set_level): PMC_LEVEL_EXACT or PMC_LEVEL_FAST
+    std::atomic<int> level{PMC_LEVEL_EXACT};
     // host-call routing (pmc_ctx_path_counts): [0] / [1] compress / decompress calls on the latency
     // path, [2] / [3] on the throughput pipeline
     uint64_t path_calls[4] = {0, 0, 0, 0};
@@ -342,8 +345,22 @@ PMC_API const char *pmc_last_error(void) { return g_err.c_str(); }
 PMC_API const char *pmc_version(void) { return "pmc_codec 0.1 gfx950 (zlib-1.2.11 level-9 gzip, bit-exact)"; }
 PMC_API size_t pmc_gzip_bound(size_t len) { return (size_t)gzip_bound(len); }
 
+// PMC_LEVEL: the initial level of every context created from now on (unset: exact).  -1: not a level.
+static int env_level() {
+    const char *e = getenv("PMC_LEVEL");
+    if (!e) return PMC_LEVEL_EXACT;
+    if (!strcmp(e, "fast") || !strcmp(e, "1")) return PMC_LEVEL_FAST;
+    if (!strcmp(e, "exact") || !strcmp(e, "9")) return PMC_LEVEL_EXACT;
+    return -1;
+}
+
 PMC_API int pmc_ctx_create(int device, pmc_ctx **out) {
     *out = nullptr;
+    const int lvl = env_level();
+    if (lvl < 0) {
+        g_err = std::string("PMC_LEVEL=") + getenv("PMC_LEVEL") + ": expected fast, 1, exact or 9";
+        return PMC_E_ARG;
+    }
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= device) {
@@ -366,6 +383,9 @@ PMC_API int pmc_ctx_create(int device, pmc_ctx **out) {
                                 (int)kLdsPerCu));
     for (const void *fk : {(const void *)deflate_front_kernel<0>, (const void *)deflate_front_kernel<1024>,
                            (const void *)deflate_front_kernel<4096>})
+        HIP_TRY(hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
+    for (const void *fk : {(const void *)deflate_front_fast_kernel<0>, (const void *)deflate_front_fast_kernel<1024>,
+                           (const void *)deflate_front_fast_kernel<4096>})
         HIP_TRY(hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
     HIP_TRY(hipFuncSetAttribute((const void *)deflate_back_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)kLdsPerCu));
@@ -402,7 +422,26 @@ PMC_API int pmc_ctx_create(int device, pmc_ctx **out) {
         return PMC_E_NO_DEVICE;
     }
     c->lane_order_ok = probe == 0;
+    if (lvl == PMC_LEVEL_FAST) {
+        // (the fast front shares the sort whose lane order the probe just checked: a context that failed it
+        // stays exact, as pmc_ctx_set_level would answer)
+        if (c->lane_order_ok) c->level = PMC_LEVEL_FAST;
+        else g_err = "PMC_LEVEL=fast ignored: the lane-order probe failed, the context stays at level 9";
+    }
     *out = c;
+    return PMC_OK;
+}
+
+PMC_API int pmc_ctx_set_level(pmc_ctx *ctx, int level) {
+    if (!ctx || (level != PMC_LEVEL_EXACT && level != PMC_LEVEL_FAST)) return PMC_E_ARG;
+    if (level == PMC_LEVEL_FAST && !ctx->lane_order_ok) return PMC_E_ARG;
+    ctx->level = level;
+    return PMC_OK;
+}
+
+PMC_API int pmc_ctx_get_level(pmc_ctx *ctx, int *level) {
+    if (!ctx || !level) return PMC_E_ARG;
+    *level = ctx->level;
     return PMC_OK;
 }
 
@@ -695,7 +734,11 @@ static int compress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t 
     // sort and codes use per-lane counters and ballots instead of returning-atomic ranks)
     // (small: a device-resident batch within the latency path's limits -- the one-kernel path, as for
     // host calls, but with the argument check and the retry pass of the device-resident API)
-    const bool mono = mono_env || latency || small || !ctx->lane_order_ok;
+    // Fast level: every value of <= 16382 bytes goes through the split pipeline with the fast front, whatever
+    // the batch (so a value's member does not depend on the entry point); longer values take the paths below
+    // unchanged.  (PMC_DEFLATE_V1, the A/B safety net, stays exact.)
+    const bool fast = ctx->level == PMC_LEVEL_FAST && ctx->lane_order_ok && !force_v1;
+    const bool mono = !fast && (mono_env || latency || small || !ctx->lane_order_ok);
     const bool split = !force_v1 && !mono;
     const uint64_t small_lim = force_v1 ? 0 : deflate_small_limit();
     const uint64_t big_lim = split ? deflate_big_limit() : small_lim;
@@ -783,12 +826,18 @@ static int compress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t 
         const size_t tl_small = (size_t)(kTreesCap + 1) * 64 * 4, tl_1k = (size_t)(kTreesCap1K + 1) * 64 * 4;
         const size_t tl_big = (size_t)(kLCodes + 1) * 64 * 4;
         // one pass over the batch for the values with lo < len <= hi, working sets sized for pcap
-        auto run_pass = [&](uint64_t lo, uint64_t hi, uint64_t pcap) -> int {
+        auto run_pass = [&](uint64_t lo, uint64_t hi, uint64_t pcap, bool fastp) -> int {
             const uint32_t fcap = front_cap_class(pcap);
-            const uint64_t fwb = deflate_front_wave_bytes(fcap ? fcap : pcap), bwb = deflate_back_wave_bytes(pcap);
-            const void *fk = fcap == 1024   ? (const void *)deflate_front_kernel<1024>
+            const uint64_t fwb = fastp ? deflate_front_fast_wave_bytes(fcap ? fcap : pcap)
+                                       : deflate_front_wave_bytes(fcap ? fcap : pcap);
+            const uint64_t bwb = deflate_back_wave_bytes(pcap);
+            const void *fk = fastp ? (fcap == 1024   ? (const void *)deflate_front_fast_kernel<1024>
+                                      : fcap == 4096 ? (const void *)deflate_front_fast_kernel<4096>
+                                                     : (const void *)deflate_front_fast_kernel<0>)
+                             : fcap == 1024 ? (const void *)deflate_front_kernel<1024>
                              : fcap == 4096 ? (const void *)deflate_front_kernel<4096>
                                             : (const void *)deflate_front_kernel<0>;
+            a.xfl = fastp ? 4u : 2u; // gzip XFL: zlib's "fastest algorithm" for a fast member
             Launch Lf = plan_lds(ctx, fk, fwb, n, 0);
             const size_t front_lds = Lf.lds;
             Launch Lb = plan_lds(ctx, (const void *)deflate_back_kernel, bwb, n, kBackTabBytes);
@@ -834,7 +883,14 @@ static int compress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t 
                 if (hipMemsetAsync(a.cQ, 0, 8, st) != hipSuccess) return PMC_E_NO_DEVICE;
                 klaunch(ctx, PMC_K_DEFLATE_FRONT, st, [&] {
                     const dim3 fg((unsigned)std::min<uint64_t>(Lf.blocks, (a.count + Lf.wpb - 1) / Lf.wpb));
-                    if (fcap == 1024)
+                    if (fastp) { // (timed as the front it stands in for)
+                        if (fcap == 1024)
+                            hipLaunchKernelGGL(deflate_front_fast_kernel<1024>, fg, dim3(64 * Lf.wpb), front_lds, st, a);
+                        else if (fcap == 4096)
+                            hipLaunchKernelGGL(deflate_front_fast_kernel<4096>, fg, dim3(64 * Lf.wpb), front_lds, st, a);
+                        else
+                            hipLaunchKernelGGL(deflate_front_fast_kernel<0>, fg, dim3(64 * Lf.wpb), front_lds, st, a);
+                    } else if (fcap == 1024)
                         hipLaunchKernelGGL(deflate_front_kernel<1024>, fg, dim3(64 * Lf.wpb), front_lds, st, a);
                     else if (fcap == 4096)
                         hipLaunchKernelGGL(deflate_front_kernel<4096>, fg, dim3(64 * Lf.wpb), front_lds, st, a);
@@ -880,10 +936,11 @@ static int compress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t 
             }
             return PMC_OK;
         };
-        r = run_pass(0, lds_cut, cap);
-        if (!r && big_pass) r = run_pass(small_lim, big_hi, big_cap);
+        r = run_pass(0, lds_cut, cap, fast);
+        if (!r && big_pass) r = run_pass(small_lim, big_hi, big_cap, false);
         if (r) return r;
         a.min_len = 0;
+        a.xfl = 2; // (everything after the small pass is exact)
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) {
             set_err("deflate split pipeline", e);
@@ -1117,6 +1174,7 @@ PMC_API int pmc_gzip_compress_batch(pmc_ctx *ctx, const uint8_t *src, const uint
     if (r) return r;
     // a server-sized batch of small values (<= 1,024 of <= 4 KiB: the host calls' latency-path limits)
     // takes the one-kernel path here too (400 x 4 KiB: 2.15 -> ~1 ms, round 5)
+    // (not at the fast level: compress_batch_body sends every batch through the split pipeline there)
     const bool small = n <= latency_batch() && max_len <= latency_max_len();
     r = compress_batch_body(ctx, src, src_off, src_len, n, dst, dst_off, dst_cap, dst_len, rc, max_len, stream, false,
                             small);
@@ -1321,7 +1379,9 @@ int host_batch_locked(pmc_ctx *ctx, Dir dir, const uint8_t *src, const uint64_t 
     // pipeline); its batch limit is 4,096 members / 16 MiB of output (latency_decompress:
     // round 5 measured the wave kernel still 2x ahead there).
     const uint64_t lat_max = latency_max_len(), lat_batch = latency_batch();
-    const bool latency = !force_pipeline && (dir == kCompress ? n <= lat_batch && max_len <= lat_max
+    // (a fast-level compress always takes the pipeline: the one-kernel path is exact only)
+    const bool fast = dir == kCompress && ctx->level == PMC_LEVEL_FAST && ctx->lane_order_ok;
+    const bool latency = !force_pipeline && (dir == kCompress ? !fast && n <= lat_batch && max_len <= lat_max
                                                               : latency_decompress(n, max_len, out_bytes));
     ctx->path_calls[(latency ? 0 : 2) + (dir == kCompress ? 0 : 1)]++;
     // The latency path's kernel reads its inputs from, and writes its outputs to, coherent host memory in

@@ -369,6 +369,7 @@ struct SmallWave {
     Trees *fb; // HBM scratch for the serial fallback
     PMC_LDS const uint32_t *crc_tab;
     PMC_LDS uint16_t *perm; // split back: the code-rank guard's canonical order (BackLayout::perm)
+    uint32_t xfl = 2;       // split back: gzip header byte 8 (DeflateArgs::xfl)
 #ifdef PMC_FAULT_LANE_ORDER
     uint32_t fault_rev = 0; // this value's sort takes its lanes in reverse (diagnostic build)
 #endif
@@ -2441,7 +2442,7 @@ struct SmallWave {
         wave_sync();
         if (l < 10) {
             const uint8_t hdr[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 2, 3};
-            outb[l] = hdr[l];
+            outb[l] = l == 8 ? (uint8_t)xfl : hdr[l];
         }
         wave_sync();
         stamp(0);

@@ -71,6 +71,8 @@ struct DeflateArgs {
     // these values and returns at once when there are none (a lifetime counter kept the
     // pass scanning every later batch of the context).
     uint32_t *rlist;
+    // gzip header byte 8 (XFL) the split back writes: 2 for an exact (level 9) member, 4 for a fast one
+    uint32_t xfl = 2;
 };
 
 // A path declines value v (rc = kDeflateRetry): the gated HBM pass of this call redoes it.
@@ -225,6 +227,10 @@ inline uint32_t front_cap_class(uint64_t pcap) {
     if (!PMC_FRONT_CAPC) return 0u;
     return pcap > 512 && pcap <= 1024 ? 1024u : pcap > 3072 && pcap <= 4096 ? 4096u : 0u;
 }
+// the fast level's front (pmc_deflate_fast.hip): same contract and cap classes as deflate_front_kernel
+uint64_t deflate_front_fast_wave_bytes(uint64_t n);
+template <uint32_t CAPC>
+__global__ void deflate_front_fast_kernel(DeflateArgs a);
 template <int CAP>
 __global__ void deflate_trees_kernel(DeflateArgs a);
 __global__ void deflate_back_kernel(DeflateArgs a);

@@ -92,7 +92,13 @@ SIGNATURES = {
     "pmc_ctx_guard_counts": (_c.c_int, [_p, _c.POINTER(_u32)]),
     "pmc_ctx_path_counts": (_c.c_int, [_p, _c.POINTER(_u64)]),
     "pmc_ctx_latency_redone": (_c.c_int, [_p, _c.POINTER(_u64)]),
+    "pmc_ctx_set_level": (_c.c_int, [_p, _c.c_int]),
+    "pmc_ctx_get_level": (_c.c_int, [_p, _c.POINTER(_c.c_int)]),
+    "pmc_group_set_level": (_c.c_int, [_p, _c.c_int]),
 }
+
+# compression levels (include/pmc_codec.h PMC_LEVEL_*)
+LEVEL_EXACT, LEVEL_FAST = 9, 1
 
 # pmc_ctx_kernel_times kinds (include/pmc_codec.h PMC_K_*)
 KERNEL_KINDS = ["deflate_front", "deflate_trees", "deflate_back", "deflate_mono", "deflate_hbm", "inflate_lds",
@@ -176,6 +182,23 @@ class Context:
         self.device = device
         import weakref
         self._deps = weakref.WeakSet()  # stores / slabs on this context: closed before it
+
+    @property
+    def level(self) -> int:
+        """LEVEL_EXACT (9: the reference's bytes) or LEVEL_FAST (1: a valid gzip member from the fast
+        parse, values <= 16382 B); include/pmc_codec.h "compression level".  Setting it takes effect
+        for the calls issued afterwards."""
+        v = _c.c_int(0)
+        rc = lib().pmc_ctx_get_level(self.handle, ctypes.byref(v))
+        if rc != 0:
+            raise CodecUnavailable(f"pmc_ctx_get_level failed ({rc})")
+        return v.value
+
+    @level.setter
+    def level(self, value: int):
+        rc = lib().pmc_ctx_set_level(self.handle, int(value))
+        if rc != 0:
+            raise ValueError(f"pmc_ctx_set_level({value}) = {rc}")
 
     def profile(self, enable: bool):
         """Bracket every kernel the batched calls enqueue with HIP events (diagnostics)."""
