@@ -44,7 +44,8 @@ typedef struct pmc_ctx pmc_ctx;
 
 /* Create a context on HIP device `device` (gfx950).  Returns PMC_OK or PMC_E_NO_DEVICE; PMC_E_ARG
  * (and a pmc_last_error text) when the environment variable PMC_LEVEL holds something else than
- * fast / 1 / exact / 9 (see the levels below). */
+ * fast / 1 / exact / 9 (see the levels below), or PMC_DICT names a file that is no dictionary (see
+ * "preset dictionary"). */
 int pmc_ctx_create(int device, pmc_ctx **out);
 
 /* ---- compression level ------------------------------------------------------------------
@@ -72,6 +73,58 @@ int pmc_ctx_create(int device, pmc_ctx **out);
 #define PMC_LEVEL_FAST 1
 int pmc_ctx_set_level(pmc_ctx *ctx, int level);
 int pmc_ctx_get_level(pmc_ctx *ctx, int *level);
+
+/* ---- preset dictionary ----------------------------------------------------------------------
+ * A context holds at most one dictionary of 1 .. PMC_DICT_MAX bytes (host memory at the call, copied
+ * to a device buffer the context owns).  Its id is the CRC-32 of its bytes; id 0 stands for "none".
+ * A dictionary serves small values, which have almost nothing earlier in themselves to match: the
+ * DEFLATE stream may use distances that reach into the dictionary, as if it preceded the value in the
+ * window (what zlib's raw deflate with deflateSetDictionary writes and inflateSetDictionary reads).
+ *
+ * Compress.  Only PMC_LEVEL_FAST uses the dictionary; level 9 stays the reference's bytes whether one
+ * is set or not, and setting one does not change the level.  At the fast level, with a dictionary of
+ * D bytes, a value of 1 <= len and D + len <= 16382 becomes a DICTIONARY MEMBER: one gzip-framed
+ * single-block member within pmc_gzip_bound(len) whose header bytes 4..7 (MTIME, 0 everywhere else in
+ * this library) hold the dictionary's id, little endian, and whose byte 8 is 4; CRC-32 and ISIZE are
+ * the value's.  The parse is the fast level's (tests/dict_model.py: fast_model's tables over
+ * dictionary || value, walked from position D; the dictionary's position 0 is never a candidate).
+ * A value of D + len > 16382 is compressed exactly as without a dictionary (a plain fast member up to
+ * 16382 bytes, level-9 bytes above), and a value whose sort fails the lane-order guard is redone at
+ * level 9.  A member depends on the value and the dictionary only, not on the entry point, batch
+ * size or batch position.
+ *
+ * Decompress, every entry point.  On a context with a dictionary a member is decoded behind the
+ * dictionary if and only if its header byte 3 is 0, bytes 4..7 equal the context's id and byte 8 is 4.
+ * Every other member is decoded as ever, MTIME ignored, on any context: foreign gzip files keep
+ * working, and there is no new return code.  A marked member whose ISIZE exceeds 16382 - D, or with a
+ * distance that reaches before the dictionary's first byte, gets PMC_Z_DATA_ERROR.  A dictionary
+ * member met without its dictionary (none set, or another one) is decoded plain: it fails with
+ * PMC_Z_DATA_ERROR through the distance or CRC checks (or decodes, when it happens not to reach into
+ * the dictionary) and never faults.
+ *
+ * A dictionary member is NOT readable by the reference's Decompress (nor by gzip tools).  Members in a
+ * store or slab need the dictionary they were written with: set it before reading them back, and do
+ * not change it while they live.  Several live dictionaries (rotation) are out of scope.
+ *
+ * Measured on one MI355X with a 2 KiB dictionary on JSON slices (DESIGN.md §4 "Front, fast level with a
+ * dictionary"): dictionary members are 0.64 (256 B values) and 0.67 (1 KiB) of level 9's bytes without a
+ * dictionary; compress runs at 9.2 / 21.8 GiB/s of value bytes (33 / 61 without a dictionary: the front sorts
+ * the dictionary again with every value) and decompress of dictionary members at 16.9 / 35.1 GiB/s of output
+ * (86 / 146 for plain fast members: dictionary members take the wave-per-member kernel).
+ *
+ * pmc_ctx_set_dictionary takes the context's locks and waits for the context's enqueued work; it takes
+ * effect for the calls issued after it returns (stores and slabs follow their context).  len 0 or a
+ * NULL dict clears.  A call that fails (PMC_Z_MEM_ERROR, PMC_E_NO_DEVICE) leaves the context -- for a group,
+ * every member -- with the dictionary it had.  PMC_E_ARG (no device touched) for a NULL context, len > PMC_DICT_MAX, or a
+ * dictionary whose CRC-32 is 0.  pmc_ctx_get_dictionary_id gives the id (0 = none);
+ * pmc_group_set_dictionary sets every member context, or none.
+ * The environment variable PMC_DICT=<path> gives every context created afterwards -- the default
+ * context, hence the drop-in and the servers, included -- that file's bytes as its initial dictionary;
+ * an unreadable, empty or oversized file (or one whose CRC-32 is 0) fails pmc_ctx_create with
+ * PMC_E_ARG and a pmc_last_error text before any device is touched, as a bad PMC_LEVEL does. */
+#define PMC_DICT_MAX 8192
+int pmc_ctx_set_dictionary(pmc_ctx *ctx, const void *dict, size_t len);
+int pmc_ctx_get_dictionary_id(pmc_ctx *ctx, uint32_t *id);
 void pmc_ctx_destroy(pmc_ctx *ctx);
 /* Default context (device 0), created on first use; used by the drop-in. */
 pmc_ctx *pmc_default_ctx(void);
@@ -269,6 +322,8 @@ void pmc_group_destroy(pmc_group *g);
 int pmc_group_size(pmc_group *g);
 /* pmc_ctx_set_level on every member context (all or none). */
 int pmc_group_set_level(pmc_group *g, int level);
+/* pmc_ctx_set_dictionary on every member context (all or none; see "preset dictionary"). */
+int pmc_group_set_dictionary(pmc_group *g, const void *dict, size_t len);
 /* member[i] = (key_hash[i] % num_shards) % pmc_group_size(g) */
 int pmc_group_route(pmc_group *g, const uint64_t *key_hash, uint32_t num_shards, uint32_t n, uint32_t *member);
 int pmc_group_compress_batch(pmc_group *g, const uint8_t *src, const uint64_t *src_off, const uint32_t *src_len,

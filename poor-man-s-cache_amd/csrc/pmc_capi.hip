@@ -187,6 +187,10 @@ struct pmc_ctx {
     bool lane_order_ok = true;
     // compression level of the calls issued from now on (pmc_ctx_set_level): PMC_LEVEL_EXACT or PMC_LEVEL_FAST
     std::atomic<int> level{PMC_LEVEL_EXACT};
+    // preset dictionary (pmc_ctx_set_dictionary): its bytes on the device (zero padded to a multiple of 16),
+    // length and id (CRC-32; 0 = none).  Written with host_mu and both dir_mu held, read under a dir_mu.
+    DevBuf dict;
+    uint32_t dict_len = 0, dict_id = 0;
     // host-call routing (pmc_ctx_path_counts): [0] / [1] compress / decompress calls on the latency
     // path, [2] / [3] on the throughput pipeline
     uint64_t path_calls[4] = {0, 0, 0, 0};
@@ -354,6 +358,10 @@ static int env_level() {
     return -1;
 }
 
+static int env_dictionary(std::vector<uint8_t> &bytes);
+static uint32_t host_crc32(const uint8_t *p, size_t n);
+static int set_dictionary_locked(pmc_ctx *ctx, const void *dict, size_t len, uint32_t id);
+
 PMC_API int pmc_ctx_create(int device, pmc_ctx **out) {
     *out = nullptr;
     const int lvl = env_level();
@@ -361,6 +369,8 @@ PMC_API int pmc_ctx_create(int device, pmc_ctx **out) {
         g_err = std::string("PMC_LEVEL=") + getenv("PMC_LEVEL") + ": expected fast, 1, exact or 9";
         return PMC_E_ARG;
     }
+    std::vector<uint8_t> env_dict; // PMC_DICT: checked before any device is touched, as PMC_LEVEL
+    if (env_dictionary(env_dict) < 0) return PMC_E_ARG;
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= device) {
@@ -387,6 +397,8 @@ PMC_API int pmc_ctx_create(int device, pmc_ctx **out) {
     for (const void *fk : {(const void *)deflate_front_fast_kernel<0>, (const void *)deflate_front_fast_kernel<1024>,
                            (const void *)deflate_front_fast_kernel<4096>})
         HIP_TRY(hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
+    HIP_TRY(hipFuncSetAttribute((const void *)deflate_front_fast_dict_kernel,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
     HIP_TRY(hipFuncSetAttribute((const void *)deflate_back_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)kLdsPerCu));
     HIP_TRY(hipFuncSetAttribute((const void *)deflate_trees_kernel<kTreesCap1K>,
@@ -399,6 +411,10 @@ PMC_API int pmc_ctx_create(int device, pmc_ctx **out) {
                                 (int)kLdsPerCu));
     HIP_TRY(hipFuncSetAttribute((const void *)inflate_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)kLdsPerCu));
+    HIP_TRY(hipFuncSetAttribute((const void *)inflate_dict_kernel<false>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
+    HIP_TRY(hipFuncSetAttribute((const void *)inflate_dict_kernel<true>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
     pmc_ctx *c = new pmc_ctx;
     c->device = device;
     c->cus = prop.multiProcessorCount;
@@ -428,6 +444,13 @@ PMC_API int pmc_ctx_create(int device, pmc_ctx **out) {
         if (c->lane_order_ok) c->level = PMC_LEVEL_FAST;
         else g_err = "PMC_LEVEL=fast ignored: the lane-order probe failed, the context stays at level 9";
     }
+    if (!env_dict.empty()) {
+        rc = set_dictionary_locked(c, env_dict.data(), env_dict.size(), host_crc32(env_dict.data(), env_dict.size()));
+        if (rc) {
+            pmc_ctx_destroy(c);
+            return rc;
+        }
+    }
     *out = c;
     return PMC_OK;
 }
@@ -442,6 +465,120 @@ PMC_API int pmc_ctx_set_level(pmc_ctx *ctx, int level) {
 PMC_API int pmc_ctx_get_level(pmc_ctx *ctx, int *level) {
     if (!ctx || !level) return PMC_E_ARG;
     *level = ctx->level;
+    return PMC_OK;
+}
+
+// ---- preset dictionary (include/pmc_codec.h "preset dictionary") ---------------------------------------
+static uint32_t host_crc32(const uint8_t *p, size_t n) {
+    uint32_t c = 0xFFFFFFFFu;
+    for (size_t i = 0; i < n; i++) {
+        c ^= p[i];
+        for (int k = 0; k < 8; k++) c = c & 1 ? kCrcPoly ^ (c >> 1) : c >> 1;
+    }
+    return ~c;
+}
+
+// PMC_DICT: the initial dictionary of every context created from now on.  0: unset, 1: `bytes` holds a
+// valid dictionary, -1: the file is unreadable, empty, oversized or has CRC-32 0 (g_err says which).
+static int env_dictionary(std::vector<uint8_t> &bytes) {
+    const char *path = getenv("PMC_DICT");
+    if (!path) return 0;
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        g_err = std::string("PMC_DICT=") + path + ": cannot be read";
+        return -1;
+    }
+    bytes.resize(PMC_DICT_MAX + 1);
+    const size_t n = fread(bytes.data(), 1, bytes.size(), f);
+    fclose(f);
+    bytes.resize(n);
+    if (n == 0 || n > PMC_DICT_MAX) {
+        g_err = std::string("PMC_DICT=") + path + (n ? ": more than PMC_DICT_MAX (8192) bytes" : ": empty");
+        return -1;
+    }
+    if (host_crc32(bytes.data(), n) == 0) {
+        g_err = std::string("PMC_DICT=") + path + ": CRC-32 is 0, which stands for no dictionary";
+        return -1;
+    }
+    return 1;
+}
+
+// A dictionary is set in two steps, so that a failure leaves the context with the dictionary it had:
+// dict_upload copies the bytes to a fresh buffer on the context's device and touches nothing of the context;
+// dict_wait waits for the context's enqueued work; dict_swap, which cannot fail, makes the buffer the context's.
+// (dict_wait and dict_swap: the caller holds host_mu and both dir_mu, or owns a context nobody else has seen.)
+static int dict_upload(pmc_ctx *ctx, const void *dict, size_t len, DevBuf &nb) {
+    if (!len) return PMC_OK;
+    int prev = -1;
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    int r = PMC_OK;
+    const size_t padded = (len + 15) & ~(size_t)15;
+    std::vector<uint8_t> h(padded + 16, 0);
+    memcpy(h.data(), dict, len);
+    if (hipSetDevice(ctx->device) != hipSuccess) {
+        set_err("pmc_ctx_set_dictionary", hipGetLastError());
+        r = PMC_E_NO_DEVICE;
+    } else if (!(r = nb.ensure(h.size())) && hipMemcpy(nb.p, h.data(), h.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        set_err("pmc_ctx_set_dictionary", hipGetLastError());
+        r = PMC_E_NO_DEVICE;
+    }
+    if (r) {
+        if (prev >= 0) (void)hipSetDevice(ctx->device);
+        nb.release();
+    }
+    if (prev >= 0) (void)hipSetDevice(prev);
+    return r;
+}
+static int dict_wait(pmc_ctx *ctx) {
+    int prev = -1;
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    int r = PMC_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        set_err("pmc_ctx_set_dictionary", hipGetLastError());
+        r = PMC_E_NO_DEVICE;
+    }
+    if (prev >= 0) (void)hipSetDevice(prev);
+    return r;
+}
+static void dict_swap(pmc_ctx *ctx, DevBuf &nb, size_t len, uint32_t id) { // (len 0 clears)
+    int prev = -1;
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    (void)hipSetDevice(ctx->device);
+    ctx->dict.release();
+    ctx->dict = nb;
+    nb = DevBuf();
+    ctx->dict_len = (uint32_t)len;
+    ctx->dict_id = len ? id : 0u;
+    if (prev >= 0) (void)hipSetDevice(prev);
+}
+static int set_dictionary_locked(pmc_ctx *ctx, const void *dict, size_t len, uint32_t id) {
+    DevBuf nb;
+    int r = dict_upload(ctx, dict, len, nb);
+    if (!r && (r = dict_wait(ctx))) {
+        int prev = -1;
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        (void)hipSetDevice(ctx->device);
+        nb.release();
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+    if (!r) dict_swap(ctx, nb, len, id);
+    return r;
+}
+
+PMC_API int pmc_ctx_set_dictionary(pmc_ctx *ctx, const void *dict, size_t len) {
+    if (!ctx || len > PMC_DICT_MAX) return PMC_E_ARG;
+    if (!dict) len = 0;
+    uint32_t id = 0;
+    if (len && (id = host_crc32((const uint8_t *)dict, len)) == 0) return PMC_E_ARG;
+    std::lock_guard<std::mutex> host_lock(ctx->host_mu);
+    std::lock_guard<std::recursive_mutex> c_lock(ctx->dir_mu[0]), d_lock(ctx->dir_mu[1]);
+    return set_dictionary_locked(ctx, dict, len, id);
+}
+
+PMC_API int pmc_ctx_get_dictionary_id(pmc_ctx *ctx, uint32_t *id) {
+    if (!ctx || !id) return PMC_E_ARG;
+    std::lock_guard<std::recursive_mutex> c_lock(ctx->dir_mu[0]);
+    *id = ctx->dict_id;
     return PMC_OK;
 }
 
@@ -478,6 +615,7 @@ PMC_API void pmc_ctx_destroy(pmc_ctx *c) {
     c->crcx.release();
     c->recs.release();
     c->bigl.release();
+    c->dict.release();
     c->guard.release();
     c->rlist.release();
     c->lvsel.release();
@@ -738,6 +876,9 @@ static int compress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t 
     // the batch (so a value's member does not depend on the entry point); longer values take the paths below
     // unchanged.  (PMC_DEFLATE_V1, the A/B safety net, stays exact.)
     const bool fast = ctx->level == PMC_LEVEL_FAST && ctx->lane_order_ok && !force_v1;
+    // With a dictionary (fast level only): values of D + len <= 16382 take the dictionary front, a pass of
+    // its own by length; longer ones the plain fast front (a second pass) or the exact paths, as without one.
+    const uint32_t dD = fast && ctx->dict_id ? ctx->dict_len : 0u;
     const bool mono = !fast && (mono_env || latency || small || !ctx->lane_order_ok);
     const bool split = !force_v1 && !mono;
     const uint64_t small_lim = force_v1 ? 0 : deflate_small_limit();
@@ -812,6 +953,10 @@ static int compress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t 
                    (ch + 1) * 4 + ch * 8 + kOrderBins * 4 + 64 + 1024;
         };
         uint64_t need = scratch_of(cap, chunk_of(cap));
+        // (the dictionary pass: its values' lengths and the cap of its token slabs and back)
+        const uint64_t dict_hi = dD ? std::min<uint64_t>(lds_cut, kDictSpan - dD) : 0;
+        const uint64_t dict_cap = std::min<uint64_t>(cap, (dict_hi + 63) & ~(uint64_t)63);
+        if (dD) need = std::max<uint64_t>(need, scratch_of(dict_cap, chunk_of(dict_cap)));
         if (big_pass) need = std::max<uint64_t>(need, scratch_of(big_cap, chunk_of(big_cap)));
         int r = ctx->split.ensure(need);
         if (r) return r;
@@ -826,12 +971,21 @@ static int compress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t 
         const size_t tl_small = (size_t)(kTreesCap + 1) * 64 * 4, tl_1k = (size_t)(kTreesCap1K + 1) * 64 * 4;
         const size_t tl_big = (size_t)(kLCodes + 1) * 64 * 4;
         // one pass over the batch for the values with lo < len <= hi, working sets sized for pcap
-        auto run_pass = [&](uint64_t lo, uint64_t hi, uint64_t pcap, bool fastp) -> int {
-            const uint32_t fcap = front_cap_class(pcap);
-            const uint64_t fwb = fastp ? deflate_front_fast_wave_bytes(fcap ? fcap : pcap)
-                                       : deflate_front_wave_bytes(fcap ? fcap : pcap);
+        // (dictp: the fast front behind the context's dictionary; its LDS layout follows D + hi, the token
+        // slabs, trees and back pcap as ever -- a value has at most len tokens)
+        auto run_pass = [&](uint64_t lo, uint64_t hi, uint64_t pcap, bool fastp, bool dictp) -> int {
+            const uint32_t fcap = dictp ? 0u : front_cap_class(pcap);
+            const uint64_t dcap = std::min<uint64_t>(((uint64_t)dD + hi + 63) & ~(uint64_t)63, kDictSpan);
+            const uint64_t fwb = dictp   ? deflate_front_fast_wave_bytes(dcap)
+                                 : fastp ? deflate_front_fast_wave_bytes(fcap ? fcap : pcap)
+                                         : deflate_front_wave_bytes(fcap ? fcap : pcap);
             const uint64_t bwb = deflate_back_wave_bytes(pcap);
-            const void *fk = fastp ? (fcap == 1024   ? (const void *)deflate_front_fast_kernel<1024>
+            a.dict = dictp ? (const uint8_t *)ctx->dict.p : nullptr;
+            a.dict_len = dictp ? dD : 0u;
+            a.front_cap = dictp ? (uint32_t)dcap : 0u;
+            a.mtime = dictp ? ctx->dict_id : 0u; // gzip MTIME: the dictionary's id marks a dictionary member
+            const void *fk = dictp ? (const void *)deflate_front_fast_dict_kernel
+                             : fastp ? (fcap == 1024   ? (const void *)deflate_front_fast_kernel<1024>
                                       : fcap == 4096 ? (const void *)deflate_front_fast_kernel<4096>
                                                      : (const void *)deflate_front_fast_kernel<0>)
                              : fcap == 1024 ? (const void *)deflate_front_kernel<1024>
@@ -883,7 +1037,9 @@ static int compress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t 
                 if (hipMemsetAsync(a.cQ, 0, 8, st) != hipSuccess) return PMC_E_NO_DEVICE;
                 klaunch(ctx, PMC_K_DEFLATE_FRONT, st, [&] {
                     const dim3 fg((unsigned)std::min<uint64_t>(Lf.blocks, (a.count + Lf.wpb - 1) / Lf.wpb));
-                    if (fastp) { // (timed as the front it stands in for)
+                    if (dictp) {
+                        hipLaunchKernelGGL(deflate_front_fast_dict_kernel, fg, dim3(64 * Lf.wpb), front_lds, st, a);
+                    } else if (fastp) { // (timed as the front it stands in for)
                         if (fcap == 1024)
                             hipLaunchKernelGGL(deflate_front_fast_kernel<1024>, fg, dim3(64 * Lf.wpb), front_lds, st, a);
                         else if (fcap == 4096)
@@ -936,11 +1092,17 @@ static int compress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t 
             }
             return PMC_OK;
         };
-        r = run_pass(0, lds_cut, cap, fast);
-        if (!r && big_pass) r = run_pass(small_lim, big_hi, big_cap, false);
+        if (dD) {
+            r = run_pass(0, dict_hi, dict_cap, true, true);
+            if (!r && lds_cut > dict_hi) r = run_pass(dict_hi, lds_cut, cap, true, false);
+        } else {
+            r = run_pass(0, lds_cut, cap, fast, false);
+        }
+        if (!r && big_pass) r = run_pass(small_lim, big_hi, big_cap, false, false);
         if (r) return r;
         a.min_len = 0;
         a.xfl = 2; // (everything after the small pass is exact)
+        a.mtime = 0;
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) {
             set_err("deflate split pipeline", e);
@@ -1017,6 +1179,12 @@ static int decompress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_
     hipStream_t st = (hipStream_t)stream;
     InflateArgs a{src, src_off, src_len, dst, dst_off, dst_cap, dst_len, rc, n, 0, 0, 0, nullptr, ctx->dbg ? ctx->dbg + 16 : nullptr,
                   nullptr, 0};
+    // (a context with a dictionary: the record and lane kernels leave its dictionary members to the LDS wave
+    // kernel, which decodes them behind the dictionary)
+    const uint32_t dD = ctx->dict_id ? ctx->dict_len : 0u;
+    a.dict = dD ? (const uint8_t *)ctx->dict.p : nullptr;
+    a.dict_len = dD;
+    a.dict_id = dD ? ctx->dict_id : 0u;
     // lane-per-member fast path (pmc_inflate_lane.hip), then the CRC check; whatever it
     // declines (rc = kInflateRetry) goes through the wave-per-member kernels below
     // (PMC_INFLATE_WAVE=1: everything through the wave kernels).
@@ -1129,15 +1297,49 @@ static int decompress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_
     out_cap = (out_cap + 63) & ~(uint64_t)63;
     a.lds_max_out = out_cap;
     a.lds_max_in = gzip_bound(out_cap) + 64;
+    // (the image: the dictionary, rounded to 16 bytes, in front of the plain members' out_cap bytes.  A
+    // dictionary member starts at the image's first byte and needs dD + min(capacity, ISIZE) of it: that fits
+    // while its capacity is within max_len, which a device-resident caller need not keep -- max_len bounds the
+    // decompressed sizes, a slab passes its own.  The members this pass cannot hold go to a second launch sized
+    // for the longest dictionary member, dD + ISIZE = 16382; like the HBM variant it is always launched, the
+    // lengths being device-resident, unless this pass has that size already or a host-memory caller, who
+    // knows lengths and capacities, says that no member needs it.)
+    a.dict_out = (uint32_t)(out_cap + ((dD + 15u) & ~15u));
+    const uint64_t dict_in = dD ? gzip_bound(kDictSpan - dD) + 64 : 0;
+    const bool dict_second = dD && need_hbm && (a.dict_out < kDictSpan || a.lds_max_in < dict_in);
+    a.dict_pass = 0;
+    a.dict_last = dict_second ? 0u : 1u;
     {
-        uint64_t wb = inflate_wave_bytes(false, a.lds_max_out, a.lds_max_in);
-        Launch L = plan_lds(ctx, (const void *)inflate_kernel<false>, wb, n);
+        uint64_t wb = inflate_wave_bytes(false, a.dict_out, a.lds_max_in);
+        Launch L = plan_lds(ctx, dD ? (const void *)inflate_dict_kernel<false> : (const void *)inflate_kernel<false>, wb, n);
         a.wave_bytes = wb;
-        klaunch(ctx, PMC_K_INFLATE_LDS, st,
-                [&] { hipLaunchKernelGGL(inflate_kernel<false>, dim3(L.blocks), dim3(64 * L.wpb), L.lds, st, a); });
+        klaunch(ctx, PMC_K_INFLATE_LDS, st, [&] {
+            if (dD) hipLaunchKernelGGL(inflate_dict_kernel<false>, dim3(L.blocks), dim3(64 * L.wpb), L.lds, st, a);
+            else hipLaunchKernelGGL(inflate_kernel<false>, dim3(L.blocks), dim3(64 * L.wpb), L.lds, st, a);
+        });
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) {
             set_err("inflate_kernel<lds>", e);
+            return PMC_E_NO_DEVICE;
+        }
+    }
+    if (dict_second) {
+        InflateArgs a2 = a;
+        a2.dict_pass = 1;
+        a2.dict_last = 1;
+        a2.first_img = a.dict_out;
+        a2.first_in = (uint32_t)a.lds_max_in;
+        a2.lds_max_out = (kDictSpan + 63) & ~63u;
+        a2.dict_out = (uint32_t)a2.lds_max_out;
+        a2.lds_max_in = dict_in;
+        a2.wave_bytes = inflate_wave_bytes(false, a2.dict_out, a2.lds_max_in);
+        Launch L = plan_lds(ctx, (const void *)inflate_dict_kernel<false>, a2.wave_bytes, n);
+        klaunch(ctx, PMC_K_INFLATE_LDS, st, [&] {
+            hipLaunchKernelGGL(inflate_dict_kernel<false>, dim3(L.blocks), dim3(64 * L.wpb), L.lds, st, a2);
+        });
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            set_err("inflate_dict_kernel<lds>", e);
             return PMC_E_NO_DEVICE;
         }
     }
@@ -1150,8 +1352,12 @@ static int decompress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_
         uint64_t waves = std::min<uint64_t>((uint64_t)ctx->cus * 4, n);
         a.wave_bytes = wb;
         klaunch(ctx, PMC_K_INFLATE_HBM, st, [&] {
-            hipLaunchKernelGGL(inflate_kernel<true>, dim3((unsigned)((waves + 3) / 4)), dim3(256),
-                               kCrcTabBytes + 4 * wb, st, a);
+            if (dD)
+                hipLaunchKernelGGL(inflate_dict_kernel<true>, dim3((unsigned)((waves + 3) / 4)), dim3(256),
+                                   kCrcTabBytes + 4 * wb, st, a);
+            else
+                hipLaunchKernelGGL(inflate_kernel<true>, dim3((unsigned)((waves + 3) / 4)), dim3(256),
+                                   kCrcTabBytes + 4 * wb, st, a);
         });
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) {

@@ -158,11 +158,13 @@ struct FastWave {
         return L;
     }
 
+    // (p0: the walk's first position -- 0, or the dictionary's length when `len` bytes of dictionary ||
+    // value are staged; literal tokens are stored relative to p0, in the value's coordinates)
     template <int PK>
-    __device__ __forceinline__ uint32_t walk(uint32_t len) {
+    __device__ __forceinline__ uint32_t walk(uint32_t len, uint32_t p0 = 0) {
         const uint32_t l = (uint32_t)lane_id();
-        uint32_t p = 0, ntok = 0;
-        for (uint32_t w0 = 0; w0 < len; w0 += 64) {
+        uint32_t p = p0, ntok = 0;
+        for (uint32_t w0 = p0; w0 < len; w0 += 64) {
             if (p >= w0 + 64u) continue; // a match covers the whole window
             const uint32_t x = w0 + l;
             const bool in = x < len;
@@ -200,16 +202,16 @@ struct FastWave {
             }
             p = w0 + pp;
             const uint64_t starts = (~0ull << pp0) & ballot(in) & ~cov;
-            if ((starts >> l) & 1ull) w.tok[ntok + popc_lt(starts)] = ism ? (x - q) << 16 | (mlen - 3u) : x;
+            if ((starts >> l) & 1ull) w.tok[ntok + popc_lt(starts)] = ism ? (x - q) << 16 | (mlen - 3u) : x - p0;
             ntok += (uint32_t)__builtin_popcountll(starts);
         }
         return ntok;
     }
 
     template <int PK>
-    __device__ __forceinline__ uint32_t parse(uint32_t npos, uint32_t len) {
+    __device__ __forceinline__ uint32_t parse(uint32_t npos, uint32_t len, uint32_t p0 = 0) {
         if (sflag(table<PK>(npos, len))) return kNtokRetry;
-        return walk<PK>(len);
+        return walk<PK>(len, p0);
     }
 
     // (inlined into the kernel: called through a pointer, the SmallWave would live in scratch memory)
@@ -230,6 +232,68 @@ struct FastWave {
         wave_sync_global();
         w.stamp(2);
         w.histogram(ntok, len);
+        w.stamp(6);
+        return ntok;
+    }
+
+    // ---- with a preset dictionary (DESIGN.md §4 "Front, fast level with a dictionary") ----------------
+    // The wave's byte area holds dictionary || value: the dictionary's D bytes are staged once per wave
+    // (stage_dict), every value behind them (stage_value).  The sort and table() run over all D + len
+    // bytes; the walk, the histogram and the tokens' literal positions start at D.
+
+    // (`dict` is the context's buffer: 16-byte aligned, zero padded to a multiple of 4 bytes)
+    __device__ __forceinline__ void stage_dict(const uint8_t *dict, uint32_t D) {
+        PMC_GLB const uint32_t *d4 = (PMC_GLB const uint32_t *)dict;
+        for (uint32_t k = (uint32_t)lane_id(); k < (D + 3) >> 2; k += 64) w.bw[k] = d4[k];
+        wave_sync();
+    }
+    // value bytes to b[D, D + len), zeros on to the padded end (as SmallWave::stage); the word that
+    // straddles D keeps its dictionary bytes.  Source dwords are read aligned, and only those that hold
+    // at least one byte of the value: unlike SmallWave::stage this reads up to 3 bytes before src and up to
+    // 3 past src + len, on purpose -- an aligned dword lies in the page of the value byte it holds, and the
+    // bytes outside the value are masked off (keep) before the store.
+    __device__ __forceinline__ void stage_value(const uint8_t *src, uint32_t len, uint32_t D) {
+        const uint32_t T = D + len, k1 = ((T + 32) & ~3u) >> 2;
+        const uintptr_t sa = (uintptr_t)src - D; // where byte 0 of the concatenation would lie
+        const uint32_t sh = (uint32_t)(sa & 3);
+        const uintptr_t g = sa & ~(uintptr_t)3;  // dword k of g holds concatenation bytes 4 k - sh ..
+        for (uint32_t k = (D >> 2) + (uint32_t)lane_id(); k < k1; k += 64) {
+            const int32_t c0 = (int32_t)(4u * k) - (int32_t)sh;
+            const bool inlo = c0 + 3 >= (int32_t)D && c0 < (int32_t)T;
+            const bool inhi = sh != 0u && c0 + 7 >= (int32_t)D && c0 + 4 < (int32_t)T;
+            const uint32_t lo = inlo ? *(PMC_GLB const uint32_t *)(g + 4ull * k) : 0u;
+            const uint32_t hi = inhi ? *(PMC_GLB const uint32_t *)(g + 4ull * k + 4) : 0u;
+            const uint32_t v = __builtin_amdgcn_alignbyte(hi, lo, sh);
+            const uint32_t c = 4u * k;
+            uint32_t keep = 0;
+#pragma unroll
+            for (uint32_t j = 0; j < 4; j++) keep |= (c + j >= D && c + j < T) ? 0xffu << (8 * j) : 0u;
+            const uint32_t dmask = c < D ? (1u << (8 * ((D - c) & 3u))) - 1u : 0u; // (D - c is 1..3 here)
+            const uint32_t old = c < D ? w.bw[k] & dmask : 0u;
+            w.bw[k] = old | (v & keep);
+        }
+        wave_sync();
+    }
+    __device__ __forceinline__ uint32_t run_front_dict(const uint8_t *src, uint32_t len, uint32_t D, int pk) {
+        stage_value(src, len, D);
+        w.stamp(0);
+        const uint32_t T = D + len, npos = T >= 3 ? T - 2 : 0;
+        uint32_t ntok;
+        if (npos) {
+            w.sort_positions2(npos, (PMC_LDS uint32_t *)w.CN);
+            w.stamp(1);
+            ntok = pk == 6 ? parse<6>(npos, T, D) : pk == 4 ? parse<4>(npos, T, D) : parse<0>(npos, T, D);
+            if (sflag(ntok == kNtokRetry ? 1u : 0u)) return kNtokRetry; // (sort guard: no histogram)
+        } else {
+            w.lit_run(0, 0, len);
+            ntok = len;
+        }
+        wave_sync_global();
+        w.stamp(2);
+        PMC_LDS uint8_t *b0 = w.b;
+        w.b = b0 + D; // (literal tokens are in the value's coordinates)
+        w.histogram(ntok, len);
+        w.b = b0;
         w.stamp(6);
         return ntok;
     }
@@ -298,6 +362,75 @@ __global__ void __launch_bounds__(256, 7) deflate_front_fast_kernel(DeflateArgs 
     }
     small_wave_stamps_out(w, a);
 }
+// The dictionary instance: the values of a.min_len < len <= a.lds_max_len (the host keeps
+// a.dict_len + a.lds_max_len <= 16382), each parsed behind the a.dict_len bytes at a.dict.  The LDS
+// layout, the ml packing and the sort follow a.front_cap >= a.dict_len + a.lds_max_len; the token slab's
+// stride stays a.cap_len (a value has at most len tokens).
+__global__ void __launch_bounds__(256, 7) deflate_front_fast_dict_kernel(DeflateArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int wib = threadIdx.x / 64, l = lane_id();
+    const uint64_t lcap = a.front_cap;
+    const uint32_t D = a.dict_len;
+    const FastLayout F = fast_layout(lcap);
+    uint8_t *base = lds + (uint64_t)wib * a.wave_bytes;
+    const SmallLayout L = small_layout(lcap);
+    SmallWave w;
+    small_wave_init(w, base, L, a, nullptr);
+    w.S = to_lds<uint16_t>(base + F.S);
+    w.R = to_lds<uint16_t>(base + F.R);
+    w.CN = to_lds<uint8_t>(base + F.X); // (the sort's 512-byte table)
+    w.s12 = F.pk == 4 ? 1u : 0u;
+    w.lfreq = to_lds<uint32_t>(base + F.freq);
+    w.dfreq = w.lfreq + 288;
+    w.blfreq = w.dfreq + 32;
+    FastWave fw{w, to_lds<uint8_t>(base + F.ml)};
+    fw.stage_dict(a.dict, D);
+    const uint32_t kBatch = a.front_batch;
+    uint32_t nx = l == 0 ? atomicAdd(a.cQ, kBatch) : 0u;
+    for (;;) {
+        const uint64_t g = readlane(nx, 0);
+        if (g >= a.count) break;
+        nx = l == 0 ? atomicAdd(a.cQ, kBatch) : 0u;
+        const uint64_t vl = g + (uint64_t)l;
+        const bool in = (uint32_t)l < kBatch && vl < a.count;
+        const uint32_t myl = in ? a.src_len[a.first + vl] : 0u;
+        const uint64_t myo = in ? a.src_off[a.first + vl] : 0u;
+        // (D + len <= front_cap is what keeps every LDS index inside the wave's working set)
+        uint64_t todo = ballot(myl != 0 && myl > a.min_len && myl <= a.lds_max_len && (uint64_t)D + myl <= lcap);
+        while (todo) {
+            const int jj = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const uint64_t v = g + (uint64_t)jj;
+            const uint32_t len = readlane(myl, jj);
+            w.tok = (PMC_GLB uint32_t *)(a.cT + v * a.cap_len);
+#ifdef PMC_FAULT_LANE_ORDER
+            w.fault_rev = (uint32_t)((a.first + v) & 1);
+#endif
+            const uint8_t *vsrc = a.src + readlane64(myo, jj);
+            const uint32_t ntok = fw.run_front_dict(vsrc, len, D, F.pk);
+            if (ntok == kNtokRetry) { // the sort's lane-order guard fired: the HBM kernel redoes the value (exact)
+                if (l == 0) {
+                    a.cN[v] = kNtokRetry;
+                    a.cZ[v] = 0;
+                    atomicAdd(a.guard, 1u);
+                }
+                continue;
+            }
+            uint32_t nz = 0;
+            for (int s = l; s < kLCodes + kDCodes; s += 64) {
+                const uint32_t f = s < kLCodes ? w.lfreq[s] : w.dfreq[s - kLCodes];
+                a.cH[v * kSplitRows + s] = (uint16_t)f;
+                nz += (uint32_t)__builtin_popcountll(ballot(s < kLCodes && f != 0));
+            }
+            if (l == 0) {
+                a.cN[v] = ntok < kSymsPerBlock ? ntok : kNtokMultiBlock;
+                a.cZ[v] = nz;
+            }
+        }
+    }
+    small_wave_stamps_out(w, a);
+}
+
 template __global__ void deflate_front_fast_kernel<0>(DeflateArgs);
 template __global__ void deflate_front_fast_kernel<1024>(DeflateArgs);
 template __global__ void deflate_front_fast_kernel<4096>(DeflateArgs);

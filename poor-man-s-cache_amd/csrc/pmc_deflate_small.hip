@@ -370,6 +370,7 @@ struct SmallWave {
     PMC_LDS const uint32_t *crc_tab;
     PMC_LDS uint16_t *perm; // split back: the code-rank guard's canonical order (BackLayout::perm)
     uint32_t xfl = 2;       // split back: gzip header byte 8 (DeflateArgs::xfl)
+    uint32_t mtime = 0;     // split back: gzip header bytes 4..7 (DeflateArgs::mtime)
 #ifdef PMC_FAULT_LANE_ORDER
     uint32_t fault_rev = 0; // this value's sort takes its lanes in reverse (diagnostic build)
 #endif
@@ -2440,10 +2441,8 @@ struct SmallWave {
         PMC_STOP(22, 0)
         for (uint32_t k = l; k < out_words; k += 64) outw[k] = 0;
         wave_sync();
-        if (l < 10) {
-            const uint8_t hdr[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 2, 3};
-            outb[l] = l == 8 ? (uint8_t)xfl : hdr[l];
-        }
+        // the 10 header bytes as three words of the zeroed image: 1f 8b 08 00 | MTIME | XFL 03 (00 00)
+        if (l < 3) outw[l] = l == 0 ? 0x00088b1fu : l == 1 ? mtime : (xfl & 0xffu) | 0x300u;
         wave_sync();
         stamp(0);
         uint64_t bitpos = emit_planned(ntok, len, 80, plan, Ls);

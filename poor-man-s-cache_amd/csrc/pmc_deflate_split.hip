@@ -598,6 +598,7 @@ __global__ void __launch_bounds__(256, 5) deflate_back_kernel(DeflateArgs a) {
     w.blfreq = to_lds<uint32_t>(base + B.blfreq);
     w.perm = to_lds<uint16_t>(base + B.perm);
     w.xfl = a.xfl;
+    w.mtime = a.mtime;
     // (run_back touches only the arrays above; the rest of w still points into the larger
     // small_layout and must stay unused here)
     PMC_LDS uint8_t *Ls = to_lds<uint8_t>(base + B.ls); // code lengths from the trees kernel

@@ -101,6 +101,43 @@ PMC_API int pmc_group_set_level(pmc_group *g, int level) {
     return PMC_OK;
 }
 
+PMC_API int pmc_group_set_dictionary(pmc_group *g, const void *dict, size_t len) {
+    if (!g || len > PMC_DICT_MAX) return PMC_E_ARG;
+    if (!dict) len = 0;
+    uint32_t id = 0;
+    if (len && (id = host_crc32((const uint8_t *)dict, len)) == 0) return PMC_E_ARG;
+    // All members or none, and a failure leaves every member with the dictionary it had: the bytes go to a
+    // fresh buffer on every member's device first; then, with every member's locks held and its enqueued work
+    // waited for, the buffers are swapped in, which cannot fail.
+    const size_t G = g->ctx.size();
+    std::vector<DevBuf> nb(G);
+    auto drop = [&]() {
+        for (size_t k = 0; k < G; k++) {
+            (void)hipSetDevice(g->ctx[k]->device);
+            nb[k].release();
+        }
+    };
+    int prev = -1;
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    int r = PMC_OK;
+    for (size_t k = 0; k < G && !r; k++) r = dict_upload(g->ctx[k], dict, len, nb[k]);
+    if (!r) {
+        std::vector<std::unique_lock<std::mutex>> hl;
+        std::vector<std::unique_lock<std::recursive_mutex>> dl;
+        for (auto *c : g->ctx) {
+            hl.emplace_back(c->host_mu);
+            dl.emplace_back(c->dir_mu[0]);
+            dl.emplace_back(c->dir_mu[1]);
+        }
+        for (size_t k = 0; k < G && !r; k++) r = dict_wait(g->ctx[k]);
+        if (!r)
+            for (size_t k = 0; k < G; k++) dict_swap(g->ctx[k], nb[k], len, id);
+    }
+    if (r) drop();
+    if (prev >= 0) (void)hipSetDevice(prev);
+    return r;
+}
+
 PMC_API int pmc_group_route(pmc_group *g, const uint64_t *key_hash, uint32_t num_shards, uint32_t n,
                             uint32_t *member) {
     if (!g || !num_shards || (n && (!key_hash || !member))) return PMC_E_ARG;

@@ -800,8 +800,23 @@ struct InflateLds {
         return 0;
     }
 
-    __device__ int run(const uint8_t *src, uint32_t in_len, uint8_t *dst, uint32_t cap, uint32_t *dst_len) {
+    // D != 0: a dictionary member (in_len >= 18), `out` starting with the D bytes of its dictionary.  The
+    // member is decoded from output position D on, so a distance may reach into the dictionary but not
+    // before its first byte; CRC-32, ISIZE, the capacity verdict and the copy-out cover [D, o).
+    // (DICT false: D is the constant 0 and the code is the plain decoder's)
+    // `img`: the bytes of `out` a dictionary member may use (>= D + min(ucap, ISIZE), the caller's routing).
+    template <bool DICT>
+    __device__ int run(const uint8_t *src, uint32_t in_len, uint8_t *dst, uint32_t ucap, uint32_t *dst_len,
+                       uint32_t dict_len = 0, uint32_t img = 0) {
+        const uint32_t D = DICT ? dict_len : 0u;
         const int l = lane_id();
+        // (the bound of the writes into the image: a dictionary member's output ends at kDictSpan, at the
+        // capacity, and in any case inside the image)
+        uint32_t cap = ucap;
+        if (D) {
+            cap = D + (ucap < kDictSpan - D ? ucap : kDictSpan - D);
+            cap = cap < img ? cap : img;
+        }
         // 1. stage input, zero padded by 64 bytes
         {
             const uint32_t words = (in_len + 64 + 3) >> 2;
@@ -860,11 +875,16 @@ struct InflateLds {
         hrc = rfl(hrc);
         if (hrc) return hrc;
         p = rfl(p);
+        if (D) { // a dictionary member of more than kDictSpan - D bytes does not exist
+            const uint32_t isz0 = inb[in_len - 4] | ((uint32_t)inb[in_len - 3] << 8) | ((uint32_t)inb[in_len - 2] << 16) |
+                                  ((uint32_t)inb[in_len - 1] << 24);
+            if (isz0 > kDictSpan - D) return PMC_Z_DATA_ERROR_DEV;
+        }
         stamp(0);
         const uint32_t nbits = in_len * 8;
         SBits sb{inw, 0, 0, 0, nbits};
         sb.seek(p * 8);
-        uint32_t o = 0; // bytes produced (uniform)
+        uint32_t o = D; // bytes in the image (uniform): the dictionary's, then those produced
         uint32_t last;
         do {
             sb.refill();
@@ -1056,19 +1076,37 @@ struct InflateLds {
         // 3. trailer: CRC-32 then ISIZE (inflate.c CHECK / LENGTH)
         const uint32_t tp = (sb.pos() + 7) >> 3;
         if (in_len < tp + 4) return PMC_Z_BUF_ERROR_DEV;
-        if (o > cap) { // a valid stream so far that needs more room: report the size (no verdict yet)
-            if (l == 0) *dst_len = o;
+        if (D && o > kDictSpan) return PMC_Z_DATA_ERROR_DEV; // (more than the ISIZE checked above)
+        if (D ? o - D > ucap : o > cap) { // a valid stream so far that needs more room: report the size (no verdict yet)
+            if (l == 0) *dst_len = o - D;
             return PMC_E_CAPACITY_DEV;
         }
-        const uint32_t crc = wave_crc32(out, o, crc_tab);
+        // (within the capacity but past the image, which holds min(capacity, ISIZE): more than ISIZE says)
+        if (D && o > cap) return PMC_Z_DATA_ERROR_DEV;
+        const uint32_t crc = wave_crc32(out + D, o - D, crc_tab);
         const uint32_t want = inb[tp] | ((uint32_t)inb[tp + 1] << 8) | ((uint32_t)inb[tp + 2] << 16) |
                               ((uint32_t)inb[tp + 3] << 24);
         if (crc != want) return PMC_Z_DATA_ERROR_DEV;
         if (in_len < tp + 8) return PMC_Z_BUF_ERROR_DEV;
         const uint32_t isz = inb[tp + 4] | ((uint32_t)inb[tp + 5] << 8) | ((uint32_t)inb[tp + 6] << 16) |
                              ((uint32_t)inb[tp + 7] << 24);
-        if (isz != o) return PMC_Z_DATA_ERROR_DEV;
+        if (isz != o - D) return PMC_Z_DATA_ERROR_DEV;
         // 4. copy-out
+        if (D) { // (the value starts at any byte of the image: dwords by alignbyte)
+            const uint32_t n = o - D, full = n >> 2, w0 = D >> 2, sh = D & 3;
+            if ((((uintptr_t)dst) & 3) == 0) {
+                uint32_t *d4 = reinterpret_cast<uint32_t *>(dst);
+                PMC_LDS const uint32_t *o4 = (PMC_LDS const uint32_t *)out;
+                for (uint32_t k = l; k < full; k += 64)
+                    d4[k] = __builtin_amdgcn_alignbyte(o4[w0 + k + 1], o4[w0 + k], sh);
+                if ((uint32_t)l < (n & 3)) dst[full * 4 + l] = out[D + full * 4 + l];
+            } else {
+                for (uint32_t k = l; k < n; k += 64) dst[k] = out[D + k];
+            }
+            if (l == 0) *dst_len = n;
+            stamp(5);
+            return 0;
+        }
         if ((((uintptr_t)dst) & 3) == 0) {
             uint32_t *d4 = reinterpret_cast<uint32_t *>(dst);
             PMC_LDS const uint32_t *o4 = (PMC_LDS const uint32_t *)out;
@@ -1084,8 +1122,10 @@ struct InflateLds {
     }
 };
 
-template <bool kHbm>
-__global__ void __launch_bounds__(256, 5) inflate_kernel(InflateArgs a) {
+// kDict: the instance a context with a dictionary launches (inflate_dict_kernel); without one the body is
+// the plain kernel's, instruction for instruction.
+template <bool kHbm, bool kDict>
+__device__ __forceinline__ void inflate_body(InflateArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     uint32_t *crc_tab = reinterpret_cast<uint32_t *>(lds);
     for (int k = threadIdx.x; k < 256; k += blockDim.x) crc_tab[k] = c_crc_table[k];
@@ -1104,7 +1144,8 @@ __global__ void __launch_bounds__(256, 5) inflate_kernel(InflateArgs a) {
         Wh.crc_tab = crc_tab;
         for (int k = 0; k < 8; k++) Wh.st[k] = 0;
     } else {
-        const InfLdsLayout L = inf_lds_layout(a.lds_max_out, a.lds_max_in);
+        // (a.dict_out: a.lds_max_out, plus the 16-byte-rounded dictionary in front when the context has one)
+        const InfLdsLayout L = inf_lds_layout(a.dict_out, a.lds_max_in);
         Wl.T = (PMC_LDS InfTables *)(base + L.tab);
         Wl.inb = to_lds<uint8_t>(base + L.in);
         Wl.inw = to_lds<uint32_t>(base + L.in);
@@ -1113,6 +1154,17 @@ __global__ void __launch_bounds__(256, 5) inflate_kernel(InflateArgs a) {
         Wl.lenv = l < 29 ? (uint32_t)c_lbase[l] | (uint32_t)c_lext[l] << 16 : 0u;
         Wl.distv = l < 30 ? (uint32_t)c_dbase[l] | (uint32_t)c_dext[l] << 16 : 0u;
         for (int k = 0; k < 8; k++) Wl.st[k] = 0;
+    }
+    // With a dictionary the image is dictionary | plain members' output: the dictionary is written once per
+    // wave, a dictionary member decodes right behind its last byte, any other member from out_plain on.
+    const uint32_t dict_id = kDict ? a.dict_id : 0u, D = kDict && dict_id ? a.dict_len : 0u;
+    PMC_LDS uint8_t *const out_dict = kHbm ? nullptr : Wl.out;
+    PMC_LDS uint8_t *const out_plain = kHbm ? nullptr : Wl.out + ((D + 15u) & ~15u);
+    if (kDict && !kHbm && D) {
+        PMC_GLB const uint32_t *d4 = (PMC_GLB const uint32_t *)a.dict;
+        PMC_LDS uint32_t *o4 = (PMC_LDS uint32_t *)out_dict;
+        for (uint32_t k = (uint32_t)l; k < (D + 3) >> 2; k += 64) o4[k] = d4[k];
+        wave_sync();
     }
 #ifdef PMC_STAMPS
     Wh.t_last = Wl.t_last = __builtin_amdgcn_s_memtime();
@@ -1128,9 +1180,32 @@ __global__ void __launch_bounds__(256, 5) inflate_kernel(InflateArgs a) {
             my_in = a.src_len[vl];
             my_cap = a.dst_cap[vl];
         }
-        const bool my_fits = my_cap <= a.lds_max_out && my_in <= a.lds_max_in;
         const bool mine = in && (!a.retry_only || a.rc[vl] == kInflateRetry);
-        uint64_t todo = ballot(mine && (kHbm != my_fits));
+        // Dictionary members are the LDS variant's whatever their capacity: a member writes at most
+        // min(capacity, ISIZE) bytes behind the dictionary (run<true> checks the rest), and it is decoded by the
+        // pass whose image and staged input hold that (fit).  One that the first pass cannot hold waits for the
+        // second, which is sized for the longest dictionary member and sees only those; one that the last pass
+        // cannot stage is longer than any member of this library and gets its verdict from ISIZE alone (nofit).
+        bool my_mark = false, my_skip = false, my_nofit = false;
+        if (kDict && dict_id != 0u && mine) {
+            const uint8_t *m = a.src + a.src_off[vl];
+            my_mark = dict_member(m, my_in, dict_id);
+            if (my_mark && !kHbm) {
+                uint32_t isz = m[my_in - 4] | (uint32_t)m[my_in - 3] << 8 | (uint32_t)m[my_in - 2] << 16 |
+                               (uint32_t)m[my_in - 1] << 24;
+                if (isz > kDictSpan - D) isz = 0; // (PMC_Z_DATA_ERROR before a byte is written)
+                const uint32_t need = D + (my_cap < isz ? my_cap : isz);
+                const bool fit = my_in <= a.lds_max_in && need <= a.dict_out;
+                const bool fit1 = my_in <= a.first_in && need <= a.first_img;
+                if (a.dict_pass) my_skip = fit1; // (the first pass decoded it)
+                else my_skip = !fit && !a.dict_last;
+                my_nofit = !fit && !my_skip;
+            }
+        }
+        if (kDict && !kHbm && a.dict_pass && !my_mark) my_skip = true; // (the second pass: dictionary members only)
+        const bool my_fits = my_mark || (my_cap <= a.lds_max_out && my_in <= a.lds_max_in);
+        uint64_t todo = ballot(mine && !my_skip && (kHbm != my_fits));
+        const uint64_t marks = ballot(my_mark), nofits = ballot(my_nofit);
         while (todo) {
             const int j = __builtin_ctzll(todo);
             todo &= todo - 1;
@@ -1152,8 +1227,19 @@ __global__ void __launch_bounds__(256, 5) inflate_kernel(InflateArgs a) {
                 Wh.inb = const_cast<uint8_t *>(src);
                 Wh.out = dst;
                 rc = Wh.run(src, in_len, dst, cap, a.dst_len + v);
+            } else if (kDict && ((marks >> j) & 1)) {
+                if ((nofits >> j) & 1) {
+                    const uint32_t isz = src[in_len - 4] | (uint32_t)src[in_len - 3] << 8 |
+                                         (uint32_t)src[in_len - 2] << 16 | (uint32_t)src[in_len - 1] << 24;
+                    rc = isz <= kDictSpan - D && isz > cap ? PMC_E_CAPACITY_DEV : PMC_Z_DATA_ERROR_DEV;
+                    if (rc == PMC_E_CAPACITY_DEV && l == 0) a.dst_len[v] = isz;
+                } else {
+                    Wl.out = out_dict;
+                    rc = Wl.template run<true>(src, in_len, dst, cap, a.dst_len + v, D, a.dict_out);
+                }
             } else {
-                rc = Wl.run(src, in_len, dst, cap, a.dst_len + v);
+                if (kDict) Wl.out = out_plain;
+                rc = Wl.template run<false>(src, in_len, dst, cap, a.dst_len + v);
             }
             if (l == 0) {
                 a.rc[v] = rc;
@@ -1168,7 +1254,17 @@ __global__ void __launch_bounds__(256, 5) inflate_kernel(InflateArgs a) {
 #endif
 }
 
+template <bool kHbm>
+__global__ void __launch_bounds__(256, 5) inflate_kernel(InflateArgs a) {
+    inflate_body<kHbm, false>(a);
+}
+template <bool kHbm>
+__global__ void __launch_bounds__(256, 5) inflate_dict_kernel(InflateArgs a) {
+    inflate_body<kHbm, true>(a);
+}
 template __global__ void inflate_kernel<false>(InflateArgs);
 template __global__ void inflate_kernel<true>(InflateArgs);
+template __global__ void inflate_dict_kernel<false>(InflateArgs);
+template __global__ void inflate_dict_kernel<true>(InflateArgs);
 
 } // namespace pmc

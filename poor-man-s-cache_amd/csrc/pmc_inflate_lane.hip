@@ -560,6 +560,8 @@ __global__ void __launch_bounds__(64) inflate_lane_kernel(InflateArgs a) {
         bool wide = false;  // declined only for the lit/len list's length: the wide pass takes it
         bool multi = false; // declined only for having several blocks: the multi-block pass takes it
         uint32_t blast = 1; // MB: the current block is the member's last
+        // (a context with a dictionary: its dictionary members are the wave kernel's)
+        if (a.dict_id != 0u && st == 0 && dict_member(in.p, in_len, a.dict_id)) st = 2;
         if (st == 0 && !lane_prepare<Cols>(in, col, bcol, lit, dist, fixed, &wide, kLaneWideLit, kLaneDistCap, &multi,
                                            MB ? &blast : nullptr))
             st = multi && a.multi_pass ? 7u : kWide || MB || !wide ? 2u : 5u;

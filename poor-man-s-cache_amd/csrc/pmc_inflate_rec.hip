@@ -281,6 +281,8 @@ __global__ void __launch_bounds__(64) inflate_rec_kernel(InflateArgs a) {
                 else if (isz > a.rec_max_out) st = 4;
             }
         }
+        // (a context with a dictionary: its dictionary members are the wave kernel's)
+        if (a.dict_id != 0u && st != 3 && in_len >= 18 && dict_member(in.p, in_len, a.dict_id)) st = 2;
 #if PMC_REC8
         LaneCode8 lit;
         LaneCode<15, int16_t, uint8_t> dist;

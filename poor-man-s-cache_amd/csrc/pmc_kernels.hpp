@@ -73,6 +73,15 @@ struct DeflateArgs {
     uint32_t *rlist;
     // gzip header byte 8 (XFL) the split back writes: 2 for an exact (level 9) member, 4 for a fast one
     uint32_t xfl = 2;
+    // gzip header bytes 4..7 (MTIME, little endian) the split back writes: 0, or the dictionary's id for a
+    // dictionary member (include/pmc_codec.h "preset dictionary")
+    uint32_t mtime = 0;
+    // the dictionary front (deflate_front_fast_dict_kernel): the context's dictionary (device memory, 16-byte
+    // aligned, zero padded to a multiple of 4 bytes), its length, and the capacity its LDS layout follows
+    // (>= dict_len + lds_max_len)
+    const uint8_t *dict = nullptr;
+    uint32_t dict_len = 0;
+    uint32_t front_cap = 0;
 };
 
 // A path declines value v (rc = kDeflateRetry): the gated HBM pass of this call redoes it.
@@ -190,7 +199,32 @@ struct InflateArgs {
     uint32_t verify_group; // verify kernel: members per wave (a power of two <= 64; 0 = 64)
     uint32_t *big_list;    // record kernel appends the members it leaves to the lane kernel (kInflateBig) here,
     uint32_t *big_count;   // counted here; the lane passes after it then visit that list only (or null: all n)
+    // preset dictionary (include/pmc_codec.h): a member whose header bytes 3..8 are 0, dict_id (little endian), 4
+    // is decoded by inflate_kernel<false> behind the dict_len bytes at dict; the record and lane kernels hand
+    // such members to it.  dict_id 0: no dictionary, no header test.  (dict: device memory, 16-byte aligned,
+    // zero padded to a multiple of 4 bytes)
+    const uint8_t *dict = nullptr;
+    uint32_t dict_len = 0;
+    uint32_t dict_id = 0;
+    // the LDS variant's output image in bytes: lds_max_out, plus the 16-byte-rounded dictionary in front when
+    // the context has one.  A dictionary member is decoded by the pass whose image holds dict_len +
+    // min(capacity, ISIZE) and whose staged input holds the member: dict_pass 0 takes those that fit it and,
+    // unless dict_last, leaves the others to dict_pass 1, which is sized for the longest dictionary member,
+    // takes dictionary members only, and skips those that fitted the first pass's first_img / first_in.
+    uint32_t dict_out = 0;
+    uint32_t dict_pass = 0, dict_last = 1;
+    uint32_t first_img = 0, first_in = 0;
 };
+
+// the members a dictionary context decodes behind its dictionary: FLG 0, MTIME = id, XFL 4 (in_len >= 18)
+template <class BytePtr>
+__device__ inline bool dict_member(BytePtr m, uint32_t in_len, uint32_t id) {
+    if (in_len < 18) return false;
+    const uint32_t mt = m[4] | (uint32_t)m[5] << 8 | (uint32_t)m[6] << 16 | (uint32_t)m[7] << 24;
+    return m[3] == 0 && m[8] == 4 && mt == id;
+}
+// the longest value a dictionary of D bytes is used for (D + len <= 16382)
+constexpr uint32_t kDictSpan = 16382;
 
 // lane-inflate visit order: member indices grouped by compressed length, so a wave's 64
 // lanes decode members of similar length and finish their decode loops together
@@ -231,11 +265,17 @@ inline uint32_t front_cap_class(uint64_t pcap) {
 uint64_t deflate_front_fast_wave_bytes(uint64_t n);
 template <uint32_t CAPC>
 __global__ void deflate_front_fast_kernel(DeflateArgs a);
+// the fast front behind a preset dictionary (runtime layout for DeflateArgs::front_cap)
+__global__ void deflate_front_fast_dict_kernel(DeflateArgs a);
 template <int CAP>
 __global__ void deflate_trees_kernel(DeflateArgs a);
 __global__ void deflate_back_kernel(DeflateArgs a);
 template <bool kHbm>
 __global__ void inflate_kernel(InflateArgs a);
+// the same for a context with a preset dictionary (InflateArgs::dict_id != 0): the LDS variant decodes the
+// dictionary members behind the dictionary, the HBM variant leaves them to it
+template <bool kHbm>
+__global__ void inflate_dict_kernel(InflateArgs a);
 template <int LIT, bool MB>
 __global__ void inflate_lane_kernel(InflateArgs a);
 template <uint32_t OUT>

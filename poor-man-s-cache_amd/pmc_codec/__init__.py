@@ -95,10 +95,15 @@ SIGNATURES = {
     "pmc_ctx_set_level": (_c.c_int, [_p, _c.c_int]),
     "pmc_ctx_get_level": (_c.c_int, [_p, _c.POINTER(_c.c_int)]),
     "pmc_group_set_level": (_c.c_int, [_p, _c.c_int]),
+    "pmc_ctx_set_dictionary": (_c.c_int, [_p, _c.c_char_p, _c.c_size_t]),
+    "pmc_ctx_get_dictionary_id": (_c.c_int, [_p, _c.POINTER(_u32)]),
+    "pmc_group_set_dictionary": (_c.c_int, [_p, _c.c_char_p, _c.c_size_t]),
 }
 
 # compression levels (include/pmc_codec.h PMC_LEVEL_*)
 LEVEL_EXACT, LEVEL_FAST = 9, 1
+# the longest preset dictionary (include/pmc_codec.h PMC_DICT_MAX)
+DICT_MAX = 8192
 
 # pmc_ctx_kernel_times kinds (include/pmc_codec.h PMC_K_*)
 KERNEL_KINDS = ["deflate_front", "deflate_trees", "deflate_back", "deflate_mono", "deflate_hbm", "inflate_lds",
@@ -199,6 +204,25 @@ class Context:
         rc = lib().pmc_ctx_set_level(self.handle, int(value))
         if rc != 0:
             raise ValueError(f"pmc_ctx_set_level({value}) = {rc}")
+
+    def set_dictionary(self, dictionary):
+        """Preset dictionary of 1 .. DICT_MAX bytes (None or b"" clears it): fast-level values of
+        len(dictionary) + len <= 16382 bytes become dictionary members, which only a context holding the same
+        dictionary reads back; include/pmc_codec.h "preset dictionary".  Waits for the context's enqueued
+        work and takes effect for the calls issued afterwards."""
+        d = bytes(dictionary) if dictionary else b""
+        rc = lib().pmc_ctx_set_dictionary(self.handle, d if d else None, len(d))
+        if rc != 0:
+            raise ValueError(f"pmc_ctx_set_dictionary({len(d)} bytes) = {rc}")
+
+    @property
+    def dictionary_id(self) -> int:
+        """CRC-32 of the context's dictionary, 0 when it has none."""
+        v = _u32(0)
+        rc = lib().pmc_ctx_get_dictionary_id(self.handle, ctypes.byref(v))
+        if rc != 0:
+            raise CodecUnavailable(f"pmc_ctx_get_dictionary_id failed ({rc})")
+        return v.value
 
     def profile(self, enable: bool):
         """Bracket every kernel the batched calls enqueue with HIP events (diagnostics)."""
