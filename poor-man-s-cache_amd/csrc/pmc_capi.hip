@@ -1076,7 +1076,7 @@ static int compress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t 
                                        dim3(64), tl_big, st, a);
                 });
                 a.wave_bytes = bwb;
-                a.back_nostage = PMC_BACK_NOSTAGE && pcap <= kNostageMaxLen ? 1u : 0u;
+                a.back_nostage = pcap <= kNostageMaxLen ? 1u : 0u;
                 // the values' CRC-32 for the back (counted with the back: it is the back's work moved out)
                 if (a.back_nostage) klaunch(ctx, PMC_K_DEFLATE_BACK, st, [&] {
                     const unsigned cb = (unsigned)std::min<uint64_t>((a.count + 511) / 512, (uint64_t)ctx->cus * 4);
@@ -1218,11 +1218,8 @@ static int decompress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_
             const uint32_t rstride =
                 (uint32_t)std::min<uint64_t>(kRecMax, std::max<uint64_t>(64, ((uint64_t)max_len + 63) & ~(uint64_t)63));
             // the 1 KiB image instance when no member may decode to more (max_len: the largest capacity),
-            // else the 4 KiB one (PMC_REC_OUT1K=0: always)
-#ifndef PMC_REC_OUT1K
-#define PMC_REC_OUT1K 1
-#endif
-            const bool out1k = PMC_REC_OUT1K && max_len <= 1024;
+            // else the 4 KiB one
+            const bool out1k = max_len <= 1024;
             const void *rk = out1k ? (const void *)inflate_rec_kernel<1024> : (const void *)inflate_rec_kernel<kRecOutMax>;
             const uint32_t rlds = rec_lds_bytes(out1k ? 1024 : kRecOutMax);
             // exactly the resident blocks: a block owns its rows for the whole grid-stride loop,

@@ -119,14 +119,11 @@ struct FrontLayout {
     int pkb;             // chain-count bits packed into R's top (front_pkb), 0: CN array, -1: HC only
     uint64_t cn, hc, ev; // parse scratch in X (cn unused when pk); the sort's 512-B table at X
 };
-// PMC_FRONT_S12: at 3-4 KiB (pkb 4, positions < 4096) the sorted positions are packed as 12-bit fields
-// (8 per 3 dwords, 4 spare bytes for the read of the last field's next dword): the front's LDS per wave
-// drops from 21.4 to 19.3 KB, so a CU holds 8 waves instead of 7 (round 2 measured 6 -> 7 waves as
-// 256 -> 244 ms at 4 KiB).
-#ifndef PMC_FRONT_S12
-#define PMC_FRONT_S12 1
-#endif
-__host__ __device__ inline bool front_s12(uint64_t n) { return PMC_FRONT_S12 && front_pkb(n) == 4; }
+// At 3-4 KiB (pkb 4, positions < 4096) the sorted positions are packed as 12-bit fields (8 per 3 dwords,
+// 4 spare bytes for the read of the last field's next dword): the front's LDS per wave drops from 21.4
+// to 19.3 KB, so a CU holds 8 waves instead of 7 (round 2 measured 6 -> 7 waves as 256 -> 244 ms at
+// 4 KiB).
+__host__ __device__ inline bool front_s12(uint64_t n) { return front_pkb(n) == 4; }
 __host__ __device__ inline FrontLayout front_layout(uint64_t n) {
     auto a = [](uint64_t x) { return (x + 15) & ~(uint64_t)15; };
     FrontLayout F;
@@ -299,29 +296,12 @@ struct TreeOut {
 // chain candidates evaluated per position by the on-demand parse's wave step (the rest, when
 // needed, by search()); at most 32 (5-bit field in the eval key)
 constexpr uint32_t kPreCandLanes = 32;
-// PMC_EVAL_BPERM: each eval offset fetches its position's maximum from the position's last lane by
-// ds_bpermute instead of an LDS store by that lane and a read back
-#ifndef PMC_EVAL_BPERM
-#define PMC_EVAL_BPERM 1
-#endif
-// PMC_HC_FROM_R: with chain counts in R (PK > 0) the walk's has-candidate words are ballots of those
-// counts, so build_cn sets no HC bits (no same-word LDS atomics)
-#ifndef PMC_HC_FROM_R
-#define PMC_HC_FROM_R 1
-#endif
-// PMC_EVAL_CN1DPP: the eval's count of position x + 1 by a DPP move from lane l + 1
-#ifndef PMC_EVAL_CN1DPP
-#define PMC_EVAL_CN1DPP 1
-#endif
-// PMC_EVAL_PRED (values <= 1 KiB, PK 6): build_cn stores each position's match length with its nearest
-// candidate (capped at 32) in the spare top bits of its S entry; an eval runs deflate_slow's lazy walk over
-// those lengths for up to kPredHops fresh starts and gives lanes only to the positions that walk visits,
-// instead of to every position of the window in order (a round-6 simulation of 1 KiB JSON slices: 38.8 ->
-// 24.7 evals per value; the stamps build measured 37.5 -> 23.8).  The walk itself stays exact: a needed position the prediction left out is a
-// stop, and the next eval starts there.
-#ifndef PMC_EVAL_PRED
-#define PMC_EVAL_PRED 1
-#endif
+// Predicted eval windows (values <= 1 KiB, PK 6): build_cn stores each position's match length with its
+// nearest candidate (capped at kPredCap) in the spare top bits of its S entry; an eval runs deflate_slow's
+// lazy walk over those lengths for up to kPredHops fresh starts and gives lanes only to the positions that
+// walk visits, instead of to every position of the window in order (a round-6 simulation of 1 KiB JSON
+// slices: 38.8 -> 24.7 evals per value; the stamps build measured 37.5 -> 23.8).  The walk itself stays
+// exact: a needed position the prediction left out is a stop, and the next eval starts there.
 // (same box, 10M x 1 KiB: front 175.3 -> 173.5 ms at 3 hops, 173.9 at 4; lengths capped at 16 instead of
 // 32: 177.4 -- more misses; the hops as a scalar loop over the masks instead of per-lane precomputed
 // targets: 196 ms, the scalar unit saturated)
@@ -365,7 +345,7 @@ struct SmallWave {
     PMC_LDS uint64_t *MP;   // segment walk: positions where a lazy-improvement run ends
     PMC_GLB uint32_t *tok;
     PMC_GLB const uint32_t *hdr = nullptr; // split back: this value's tree header from the trees kernel
-    PMC_GLB const uint8_t *gsrc = nullptr; // split back (PMC_BACK_NOSTAGE): the source bytes in HBM, not staged
+    PMC_GLB const uint8_t *gsrc = nullptr; // split back, unstaged pass: the source bytes in HBM
     Trees *fb; // HBM scratch for the serial fallback
     PMC_LDS const uint32_t *crc_tab;
     PMC_LDS uint16_t *perm; // split back: the code-rank guard's canonical order (BackLayout::perm)
@@ -398,15 +378,15 @@ struct SmallWave {
 #define PMC_STOP(k, ret)
 #endif
 
-    // sorted position k: u16, or (PK 4 with PMC_FRONT_S12) bits 12 k .. 12 k + 11 of the packed words
+    // sorted position k: u16, or (PK 4, front_s12) bits 12 k .. 12 k + 11 of the packed words
     template <int PK>
     __device__ __forceinline__ uint32_t sget(uint32_t k) const {
-        if constexpr (PK == 4 && PMC_FRONT_S12) {
+        if constexpr (PK == 4) {
             PMC_LDS const uint32_t *S32 = (PMC_LDS const uint32_t *)S;
             const uint32_t bit = 12u * k, w = bit >> 5;
             return __builtin_amdgcn_alignbit(S32[w + 1], S32[w], bit & 31u) & 0xfffu;
-        } else if constexpr (PK == 6 && PMC_EVAL_PRED) {
-            return S[k] & 0x3ffu; // (bits 15:10: the nearest candidate's match length, PMC_EVAL_PRED)
+        } else if constexpr (PK == 6) {
+            return S[k] & 0x3ffu; // (bits 15:10: the nearest candidate's match length, build_cn's kPred)
         } else {
             return S[k];
         }
@@ -941,10 +921,11 @@ struct SmallWave {
     // position) strictly increasing along S -- and the caller sends the value to the retry kernel
     // (per-lane counters, no atomic order) instead of parsing chains that may point forward.
     // has-candidate bits of positions 64 w .. 64 w + 63 (uniform): with the counts in R (PK > 0) a ballot of
-    // them (one LDS read, as the HC word's), otherwise the HC word build_cn set
+    // them (one LDS read, as the HC word's), so build_cn sets no HC bits for those sizes (no same-word LDS
+    // atomics); otherwise the HC word build_cn set
     template <int PK>
     __device__ __forceinline__ uint64_t hc_word(uint32_t w, uint32_t npos) const {
-        if constexpr (PK > 0 && PMC_HC_FROM_R) {
+        if constexpr (PK > 0) {
             const uint32_t x = w * 64u + (uint32_t)lane_id();
             return ballot(x < npos && (uint32_t)R[x < npos ? x : 0u] >> (16 - PK) != 0u);
         } else {
@@ -957,14 +938,14 @@ struct SmallWave {
         const uint32_t l = (uint32_t)lane_id();
         // has-candidate bits set by position below (HC as u32 words, LDS atomics): no second
         // pass over the positions.  (PK > 0: the walk takes them from R's counts, hc_word)
-        constexpr bool kHc = !(PK > 0 && PMC_HC_FROM_R);
+        constexpr bool kHc = !(PK > 0);
         if (kHc) {
             for (uint32_t k = l; k < (npos + 63) / 64 * 2; k += 64) ((PMC_LDS uint32_t *)HC)[k] = 0u;
             wave_sync();
         }
         uint32_t ph = 0xffffffffu, prs = 0, pq = 0; // previous chunk's last hash, run start, position
         uint32_t bad = 0;
-        constexpr bool kPred = PK == 6 && PMC_EVAL_PRED;
+        constexpr bool kPred = PK == 6; // (predicted eval windows, kPredHops)
         uint32_t pa[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // (kPred) previous chunk's last 32 bytes
         for (uint32_t c0 = 0; c0 < npos; c0 += 64) {
             const uint32_t k = c0 + l;
@@ -1056,7 +1037,7 @@ struct SmallWave {
     // (5) an LDS max per position and its read-back.  Lanes outside the evaluated prefix
     // compute on clamped indices and contribute key 0 (no exec-mask branches).
     template <int PK>
-    // (pend: the walk's pending match length at p0, 2 = none; it seeds PMC_EVAL_PRED's predicted walk)
+    // (pend: the walk's pending match length at p0, 2 = none; it seeds the predicted walk of PK 6)
     __device__ void eval_group(Group &g, uint32_t p0, uint32_t npos, uint32_t len, uint32_t pend = 2) {
         // SAT: a count field narrower than kPreCand saturates below it; such a position gets
         // kPreCand lanes whose candidates are validated (same hash, inside the array, not NIL) and
@@ -1065,7 +1046,7 @@ struct SmallWave {
         constexpr bool SAT = CMAX < kPreCand;
         const uint32_t l = (uint32_t)lane_id();
         const uint32_t x = p0 + l;
-        const uint32_t xc = x < npos ? x : 0u, x1 = x + 1 < npos ? x + 1 : 0u;
+        const uint32_t xc = x < npos ? x : 0u;
         uint32_t rx = R[xc], cn, cn1;
         if (PK > 0) {
             cn = rx >> RB;
@@ -1076,19 +1057,10 @@ struct SmallWave {
             cn = CN[xc];
         }
         cn = x < npos ? cn : 0u;
-#if PMC_EVAL_CN1DPP
         // x + 1's count is lane l + 1's (one DPP move instead of an LDS read).  Lane 63 takes 1 ("x + 1 has
         // candidates"): offset 63 is then never a fast step, and the walk's general step decides it exactly.
         cn1 = (uint32_t)__builtin_amdgcn_update_dpp(1, (int)cn, 0x130, 0xf, 0xf, false); // wave_shl:1
-        (void)x1;
-#else
-        if (PK > 0) cn1 = (uint32_t)R[x1] >> RB;
-        else if (PK < 0) cn1 = (uint32_t)(HC[x1 >> 6] >> (x1 & 63)) & 1u;
-        else cn1 = CN[x1];
-        cn1 = x + 1 < npos ? cn1 : 0u;
-#endif
-        uint32_t gate = 1; // (PMC_EVAL_PRED: 0 for a position the predicted walk skips)
-#if PMC_EVAL_PRED
+        uint32_t gate = 1; // (PK 6: 0 for a position the predicted walk skips)
         if constexpr (PK == 6) {
             // deflate_slow's lazy walk from p0 over the nearest candidates' match lengths (S bits 15:10):
             // from a fresh start s it visits s .. t, t the first position after s that does not improve
@@ -1123,7 +1095,6 @@ struct SmallWave {
             if (sp < 64u) inc |= ~0ull << sp; // (past the hop limit: the rest of the window in order)
             gate = (uint32_t)(inc >> l) & 1u;
         }
-#endif
         const uint32_t w0 = gate == 0u ? 0u : SAT && cn == CMAX ? kPreCand : cn < kPreCand ? cn : kPreCand;
         const uint32_t w = w0; // lanes of this position
         const uint32_t incl = wave_incl_scan_dpp(w), offs = incl - w;
@@ -1195,22 +1166,12 @@ struct SmallWave {
             // front 194 -> 185 ms at 1 KiB).  Positions < 4096 at these sizes, so q takes 12 bits.
             const uint32_t k2 = own << 26 | (vk ? cl << 17 | (kPreCand - d) << 12 | q : 0u);
             const uint32_t mx = wave_incl_max_dpp(k2);
-#if PMC_EVAL_BPERM
             // offset l reads its maximum from its last lane, incl - 1, by one ds_bpermute (no exec-masked
             // store, wave sync and read back); an offset without lanes reads some lane's word, which nothing
             // uses (its walk masks come from the counts)
             const uint32_t m = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((incl - 1u) & 63u) << 2), (int)mx) &
                                0x3ffffffu;
             kk = (m >> 17) << 23 | ((m >> 12) & 31u) << 18 | (m & 4095u);
-#else
-            const uint32_t onx = (uint32_t)__builtin_amdgcn_update_dpp(64, (int)own, 0x130, 0xf, 0xf, false); // lane l + 1
-            if (v && (l + 1 >= nl || onx != own)) {
-                const uint32_t m = mx & 0x3ffffffu;
-                EV[own] = (m >> 17) << 23 | ((m >> 12) & 31u) << 18 | (m & 4095u);
-            }
-            wave_sync();
-            kk = EV[l];
-#endif
         } else {
             __hip_atomic_fetch_max(&EV[own], vk ? cl << 23 | (kPreCand - d) << 18 | q : 0u, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_WAVEFRONT);
@@ -2289,7 +2250,6 @@ struct SmallWave {
             // (lcode | dcode | blcode contiguous; runs is free scratch in the split back)
             if (sflag(codes_from_lengths_all(Ls, lcode, (PMC_LDS uint32_t *)runs, perm))) return kBitsGuard;
             PMC_STOP(23, bitpos)
-#if PMC_TREES_HDR
             if (sflag(hdr ? 1u : 0u)) { // the header bits the trees kernel emitted, after the 3-bit block header
                 if (l == 0) or_bits_lds(bitpos, (2u << 1) | 1u, 3);
                 bitpos += 3;
@@ -2313,7 +2273,6 @@ struct SmallWave {
                 wave_sync();
                 return bitpos;
             }
-#endif
             const int lcodes = l_max + 1, dcodes = d_max + 1, blcodes = mbi + 1;
             if (l == 0) {
                 or_bits_lds(bitpos, (2u << 1) | 1u, 3);
@@ -2428,7 +2387,7 @@ struct SmallWave {
                             uint8_t *dst, uint32_t dst_cap, uint32_t *dst_len, uint32_t crc_in, uint32_t nostage) {
         const int l = lane_id();
         uint32_t crc;
-        if (sflag(nostage)) { // (PMC_BACK_NOSTAGE: crc_in is the batch CRC pass's)
+        if (sflag(nostage)) { // (unstaged pass: crc_in is the batch CRC pass's)
             gsrc = (PMC_GLB const uint8_t *)src;
             crc = crc_in;
             PMC_STOP(21, 0)

@@ -545,7 +545,7 @@ __device__ void trees_value(const DeflateArgs &a, uint64_t v, uint64_t slot, PMC
     const uint32_t static_lenb = (stat + 3 + 7) >> 3;
     if (static_lenb <= opt_lenb) opt_lenb = static_lenb;
     const uint32_t type = len + 4 <= opt_lenb ? 0u : static_lenb == opt_lenb ? 1u : 2u;
-    const bool hdr = PMC_TREES_HDR && type == 2 && len > kHdrMinLen;
+    const bool hdr = type == 2 && len > kHdrMinLen;
     a.cP[v] = type | (uint32_t)l_max << 2 | (uint32_t)d_max << 11 | (uint32_t)mbi << 16 | (hdr ? kPlanHdr : 0u);
     if (hdr) { // (the bit-length tree's heap overwrote the front of the staged row: stage it again)
         t.stage_row();

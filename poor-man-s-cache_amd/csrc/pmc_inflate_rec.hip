@@ -51,27 +51,12 @@ static_assert(kRecFlushAt >= 4 && kRecFlushAt <= kRecStage && kRecStage % 4 == 0
 #ifndef PMC_REC_LIT
 #define PMC_REC_LIT 96
 #endif
-// PMC_REC8: the symbol lists as bytes (u16 before round 5): a literal/length symbol is its low 8 bits
-// plus the rule that in each code length's run of the (length, symbol)-sorted list the literals come
-// first, so one byte per length (the run's first entry >= 256: "split") restores the ninth bit.  The
-// columns shrink from 300 to 195 B per lane: 25.3 -> 18.6 KB of LDS per wave, 6 -> 8 waves per CU for
-// the 1 KiB image (the kernel waits on LDS and memory latency; round 2 measured 5 -> 6 waves as
+// The symbol lists are bytes (u16 before round 5): a literal/length symbol is its low 8 bits plus the
+// rule that in each code length's run of the (length, symbol)-sorted list the literals come first, so
+// one byte per length (the run's first entry >= 256: "split") restores the ninth bit.  The columns
+// shrink from 300 to 195 B per lane: 25.3 -> 18.6 KB of LDS per wave, 6 -> 8 waves per CU for the
+// 1 KiB image (the kernel waits on LDS and memory latency; round 2 measured 5 -> 6 waves as
 // 82 -> 70 ms).
-#ifndef PMC_REC8
-#define PMC_REC8 1
-#endif
-// PMC_REC_OUT1K: a batch whose outputs are all <= 1 KiB (dst_cap) runs the instance whose phase B
-// image holds 1 KiB (phase B's LDS then fits inside phase A's); others the 4 KiB image.
-// PMC_REC_DPOS: phase B keeps each record's match distance at the record's start position (in the
-// position array itself) instead of a per-record array indexed through a popcount of the start bitmap:
-// two 16-byte LDS reads per lane per 1,024 positions instead of sixteen u16 reads
-#ifndef PMC_REC_DPOS
-#define PMC_REC_DPOS 1
-#endif
-#ifndef PMC_REC_OUT1K
-#define PMC_REC_OUT1K 1
-#endif
-typedef LaneCols<PMC_REC_LIT, 24> RecCols;
 // byte-column layout per lane: lit/len and distance bases (int16 columns, entry i of lane l at u16 word
 // i * 64 + l), then byte columns (entry i at byte i * 64 + l): lit/len symbols' low bytes, the splits
 // (lengths 1..15), distance symbols
@@ -95,32 +80,29 @@ struct RecCols8 {
         b[(lit ? kSymL : kSymD) + at * 64] = (uint8_t)sym;
     }
 };
-typedef std::conditional<PMC_REC8 != 0, RecCols8, RecCols>::type RecColsK;
 static_assert((kRecStage & (kRecStage - 1)) == 0, "stage ring: a power of two");
 // phase A: code columns | input windows | record stage (the build columns live from the window on,
 // which starts only after the tables are built)
-constexpr uint32_t kRecWinOff = PMC_REC8 ? RecCols8::kBytes : (uint32_t)RecCols::kColWords * 64 * 2;
+constexpr uint32_t kRecWinOff = RecCols8::kBytes;
 static_assert(kRecWinOff % 16 == 0, "window dwords aligned");
 constexpr uint32_t kRecStageOff = kRecWinOff + kRecWinDw * 64 * 4;
 constexpr uint32_t kRecBColBytes = (kBColCl + 19) * 64;
 constexpr uint32_t kRecALds = kRecWinOff + ((kRecWinDw + kRecStage) * 64 * 4 > kRecBColBytes
                                                 ? (kRecWinDw + kRecStage) * 64 * 4 : kRecBColBytes);
-// phase B: two output images (16 B of head room so dword -1 reads) | src u16 | start bitmap |
-// per record: its match distance, or 0 for literals (whose bytes go straight to the image)
+// phase B: two output images (16 B of head room so dword -1 reads) | src u16 | start bitmap.
+// A record's match distance (0 for literals, whose bytes go straight to the image) sits at the record's
+// start position in the src array, written before the position round overwrites that position, instead
+// of a per-record array indexed through a popcount of the start bitmap: two 16-byte LDS reads per lane
+// per 1,024 positions instead of sixteen u16 reads.
+// (A batch whose outputs are all <= 1 KiB (dst_cap) runs the instance whose image holds 1 KiB: phase
+// B's LDS then fits inside phase A's; others the 4 KiB image.)
 template <uint32_t OUT>
 struct RecB {
     static constexpr uint32_t kOut0 = 16;
     static constexpr uint32_t kOut1 = kOut0 + OUT + 32;
     static constexpr uint32_t kSrc = kOut1 + OUT + 32;
     static constexpr uint32_t kBits = kSrc + 2 * OUT;
-#if PMC_REC_DPOS
-    // (a record's distance sits at its start position in the src array, written before the position round
-    // overwrites that position: no per-record array)
     static constexpr uint32_t kEnd = kBits + OUT / 8;
-#else
-    static constexpr uint32_t kRecD = kBits + OUT / 8;
-    static constexpr uint32_t kEnd = kRecD + 2 * (OUT < kRecMax ? OUT : kRecMax); // (records <= output bytes)
-#endif
     static constexpr uint32_t kLds = kEnd > kRecALds ? kEnd : kRecALds;          // phase B reuses phase A's LDS
     static_assert(OUT % 1024 == 0, "positions resolve 1024 at a time");
 };
@@ -237,9 +219,6 @@ __global__ void __launch_bounds__(64) inflate_rec_kernel(InflateArgs a) {
     PMC_LDS uint8_t *ob0 = to_lds<uint8_t>(lds + B::kOut0), *ob1 = to_lds<uint8_t>(lds + B::kOut1);
     PMC_LDS uint16_t *srcv = to_lds<uint16_t>((uint16_t *)(lds + B::kSrc));
     PMC_LDS uint32_t *bits = to_lds<uint32_t>((uint32_t *)(lds + B::kBits));
-#if !PMC_REC_DPOS
-    PMC_LDS uint16_t *recd = to_lds<uint16_t>((uint16_t *)(lds + B::kRecD));
-#endif
     const uint32_t rstride = a.rec_stride;
     PMC_GLB uint32_t *const rows = (PMC_GLB uint32_t *)a.rec_scratch + (uint64_t)blockIdx.x * 64 * rstride;
     PMC_GLB uint32_t *const row = rows + (uint64_t)lane * rstride;
@@ -283,7 +262,6 @@ __global__ void __launch_bounds__(64) inflate_rec_kernel(InflateArgs a) {
         }
         // (a context with a dictionary: its dictionary members are the wave kernel's)
         if (a.dict_id != 0u && st != 3 && in_len >= 18 && dict_member(in.p, in_len, a.dict_id)) st = 2;
-#if PMC_REC8
         LaneCode8 lit;
         LaneCode<15, int16_t, uint8_t> dist;
         {
@@ -294,19 +272,12 @@ __global__ void __launch_bounds__(64) inflate_rec_kernel(InflateArgs a) {
             dist.base = (PMC_LDS int16_t *)(col + RecCols8::kColBaseD * 64);
             dist.sym = b8 + RecCols8::kSymD;
         }
-#else
-        LaneCode<15> lit, dist;
-        lit.base = (PMC_LDS int16_t *)(col + RecCols::kColBaseL * 64);
-        lit.sym = col + RecCols::kColLit * 64;
-        dist.base = (PMC_LDS int16_t *)(col + RecCols::kColBaseD * 64);
-        dist.sym = col + RecCols::kColDist * 64;
-#endif
         bool fixed = false;
 #ifdef PMC_STAMPS
         uint64_t t0 = __builtin_amdgcn_s_memtime();
 #endif
         bool over = false;
-        if (st == 0 && !lane_prepare<RecColsK>(in, col, bcol, lit, dist, fixed, &over, kLaneWideLit, kLaneDistCap))
+        if (st == 0 && !lane_prepare<RecCols8>(in, col, bcol, lit, dist, fixed, &over, kLaneWideLit, kLaneDistCap))
             st = over ? 4u : 2u; // (lists the lane kernels hold: theirs)
 #ifdef PMC_STAMPS
         uint64_t t1 = __builtin_amdgcn_s_memtime();
@@ -562,11 +533,7 @@ __global__ void __launch_bounds__(64) inflate_rec_kernel(InflateArgs a) {
                         if (k < mr) {
                             // a literal record places its bytes now; a match keeps its distance
                             const uint32_t nl = w >> 30;
-#if PMC_REC_DPOS
                             srcv[s] = (uint16_t)(nl ? 0u : ((w >> 8) & 0x7fff) + 1); // (at the start position)
-#else
-                            recd[R + k] = (uint16_t)(nl ? 0u : ((w >> 8) & 0x7fff) + 1);
-#endif
                             lds_or(&bits[s >> 5], 1u << (s & 31));
                             if (nl) ob[s] = (uint8_t)w;
                             if (nl >= 2) ob[s + 1] = (uint8_t)(w >> 8);
@@ -575,7 +542,7 @@ __global__ void __launch_bounds__(64) inflate_rec_kernel(InflateArgs a) {
                         carry = rl(incl, 63);
                     }
                     R += mr;
-                    (void)R;
+                    (void)R; // (read by the stamps build only)
                 }
                 wave_sync();
                 // (b) the next pass's records; (c) the previous pass's images
@@ -583,11 +550,7 @@ __global__ void __launch_bounds__(64) inflate_rec_kernel(InflateArgs a) {
                 if (nm[0] >= 0) fetch(nm);
                 flush_prev();
                 // (d) positions, 1024 per round (16 per lane): record, literal byte or source position
-#if PMC_REC_DPOS
                 uint32_t carry = 0; // (start position + 1) << 16 | distance of the last record start so far
-#else
-                uint32_t before = 0;
-#endif
                 for (uint32_t c0 = 0; c0 < ext; c0 += 1024) {
                     const uint32_t p0 = c0 + 16 * lane;
                     // end of the valid positions of the lane's member
@@ -601,7 +564,6 @@ __global__ void __launch_bounds__(64) inflate_rec_kernel(InflateArgs a) {
                     }
                     const uint32_t bw = p0 < lim ? (bits[p0 >> 5] >> (p0 & 16)) & 0xffffu : 0u;
                     uint32_t sp[16];
-#if PMC_REC_DPOS
                     // the distances at the lane's 16 positions (valid at record starts) in two 16-byte
                     // reads, and the last start below the lane by a max-scan of (position, distance)
                     uint32_t dv[8];
@@ -624,22 +586,6 @@ __global__ void __launch_bounds__(64) inflate_rec_kernel(InflateArgs a) {
                         const uint32_t p = p0 + i;
                         sp[i] = p < lim && cur ? p - cur : p;
                     }
-#else
-                    const uint32_t cnt = (uint32_t)__builtin_popcount(bw);
-                    const uint32_t incl = wave_incl_scan_dpp(cnt);
-                    const uint32_t base = before + incl - cnt; // record starts before p0
-                    before += rl(incl, 63);
-#pragma unroll
-                    for (int i = 0; i < 16; i++) {
-                        const uint32_t pr = base + (uint32_t)__builtin_popcount(bw & ((2u << i) - 1));
-                        sp[i] = recd[pr ? pr - 1 : 0u];
-                    }
-#pragma unroll
-                    for (int i = 0; i < 16; i++) {
-                        const uint32_t p = p0 + i;
-                        sp[i] = p < lim && sp[i] ? p - sp[i] : p;
-                    }
-#endif
                     // (a lane reads and then rewrites only its own 16 positions of src: no sync needed here)
                     uint32_t sw[8];
 #pragma unroll

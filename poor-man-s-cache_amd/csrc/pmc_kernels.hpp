@@ -45,9 +45,9 @@ struct DeflateArgs {
     uint32_t *cN;  // token count per value
     uint16_t *cH;  // symbol histograms, [value][kSplitRows]
     uint8_t *cL;   // code lengths lit/len | dist | bit-length, [value][kSplitRows]
-    uint32_t *cB;  // dynamic-block tree headers from the trees kernel, [value][kHdrWords] (PMC_TREES_HDR)
-    uint32_t *cC;  // CRC-32 of each value of the chunk, from crc32_batch_kernel (PMC_BACK_NOSTAGE)
-    uint32_t back_nostage; // this pass's back reads cC and the source in HBM instead of staging (PMC_BACK_NOSTAGE)
+    uint32_t *cB;  // dynamic-block tree headers from the trees kernel, [value][kHdrWords] (values > kHdrMinLen)
+    uint32_t *cC;  // CRC-32 of each value of the chunk, from crc32_batch_kernel (unstaged passes)
+    uint32_t back_nostage; // this pass's back reads cC and the source in HBM instead of staging (caps <= kNostageMaxLen)
     uint32_t *cP;  // block plan per value
     uint32_t *cG;  // trees kernel merge lists, interleaved [block][kMergeRows][64]
     uint32_t *cD;  // values deferred to the large-heap trees pass; their number at cD[count]
@@ -135,22 +135,16 @@ constexpr uint32_t kMergeRows = 572;  // 2 heap entries per merge, <= 285 merges
 // a dynamic block's tree header (HLIT..send_tree, at most 14 + 19 * 3 + 316 * 7 = 2283 bits): word 0 the
 // bit count, then the bits LSB-first (76 words: 16-byte rows)
 constexpr uint32_t kHdrWords = 76;
-// PMC_TREES_HDR: for values of more than kHdrMinLen bytes the trees kernel (one lane per value) emits the
-// header bits and sets kPlanHdr in the plan; the back copies them.  (Same box, 10M x 1 KiB: trees 20.6 ->
-// 27.8 ms, back 36.7 -> 26.3; 1M x 4 KiB: -1.2 ms; at 256 B the trees' cost exceeded the back's saving,
-// +6.8 / -5.4 ms, so smaller values keep the back's wave-wide headers.)
-#ifndef PMC_TREES_HDR
-#define PMC_TREES_HDR 1
-#endif
+// For values of more than kHdrMinLen bytes the trees kernel (one lane per value) emits the header bits and
+// sets kPlanHdr in the plan; the back copies them.  (Same box, 10M x 1 KiB: trees 20.6 -> 27.8 ms, back
+// 36.7 -> 26.3; 1M x 4 KiB: -1.2 ms; at 256 B the trees' cost exceeded the back's saving, +6.8 / -5.4 ms,
+// so smaller values keep the back's wave-wide headers.)
 constexpr uint32_t kHdrMinLen = 512, kPlanHdr = 1u << 21;
-// PMC_BACK_NOSTAGE: for passes of values of <= kNostageMaxLen bytes the back stages no source bytes: their
-// CRC-32 comes from a batch CRC pass before it (the verify kernel's method) and a literal token's byte is
-// read from the source in HBM (L2: the back's prefetch has touched its lines).  Same box: 10M x 256 B back
-// 23.35 -> 21.5 ms (CRC pass included); at 1 KiB 26.3 -> 27.65 and 4 KiB 11.4 -> 14.15, so larger values
-// keep the staged bytes and the back's own CRC.
-#ifndef PMC_BACK_NOSTAGE
-#define PMC_BACK_NOSTAGE 1
-#endif
+// For passes of values of <= kNostageMaxLen bytes the back stages no source bytes: their CRC-32 comes from
+// a batch CRC pass before it (the verify kernel's method) and a literal token's byte is read from the
+// source in HBM (L2: the back's prefetch has touched its lines).  Same box: 10M x 256 B back 23.35 ->
+// 21.5 ms (CRC pass included); at 1 KiB 26.3 -> 27.65 and 4 KiB 11.4 -> 14.15, so larger values keep the
+// staged bytes and the back's own CRC.
 constexpr uint32_t kNostageMaxLen = 512;
 constexpr uint32_t kPlanDeferred = 0xffffffffu;
 #ifndef PMC_TREES_CAP
@@ -254,11 +248,7 @@ uint64_t deflate_back_wave_bytes(uint64_t n);
 template <uint32_t CAPC>
 __global__ void deflate_front_kernel(DeflateArgs a);
 // the front instance for a pass of cap pcap: 1024 / 4096 (compile-time layout) or 0 (runtime layout)
-#ifndef PMC_FRONT_CAPC
-#define PMC_FRONT_CAPC 1
-#endif
 inline uint32_t front_cap_class(uint64_t pcap) {
-    if (!PMC_FRONT_CAPC) return 0u;
     return pcap > 512 && pcap <= 1024 ? 1024u : pcap > 3072 && pcap <= 4096 ? 4096u : 0u;
 }
 // the fast level's front (pmc_deflate_fast.hip): same contract and cap classes as deflate_front_kernel

@@ -1,4 +1,5 @@
-"""CPU model of the front's eval-window policies on JSON-slice values (round 6, PMC_EVAL_PRED).
+"""CPU model of the front's eval-window policies on JSON-slice values (round 6: the predicted eval
+windows the front uses for values <= 1 KiB, build_cn's kPred and eval_group in pmc_deflate_small.hip).
 
 Runs zlib deflate_slow (level 9: max_chain 4096, good 32, nice 258, lazy 258) on random slices of the
 reference's tests/data corpus to get the positions the parse searches, then replays the front's evals:
