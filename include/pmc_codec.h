@@ -44,12 +44,12 @@ typedef struct pmc_ctx pmc_ctx;
 
 /* Create a context on HIP device `device` (gfx950).  Returns PMC_OK or PMC_E_NO_DEVICE; PMC_E_ARG
  * (and a pmc_last_error text) when the environment variable PMC_LEVEL holds something else than
- * fast / 1 / exact / 9 (see the levels below), or PMC_DICT names a file that is no dictionary (see
+ * fast / 1 / fast-all / 2 / exact / 9 (see the levels below), or PMC_DICT names a file that is no dictionary (see
  * "preset dictionary"). */
 int pmc_ctx_create(int device, pmc_ctx **out);
 
 /* ---- compression level ------------------------------------------------------------------
- * A context compresses at one of two levels:
+ * A context compresses at one of three levels:
  *   PMC_LEVEL_EXACT (9, the default): the reference's bytes, as stated above.
  *   PMC_LEVEL_FAST (1): every value of at most 16382 bytes is parsed by a GPU-shaped match finder
  *     (two hash candidates per position, matches found up to 32 bytes and extended when taken, a
@@ -61,16 +61,35 @@ int pmc_ctx_create(int device, pmc_ctx **out);
  *     (a fast-level compress never takes the one-kernel latency path).  Values above 16382 bytes take
  *     the exact paths unchanged and come out as the reference's bytes (header byte 8 = 2); so does a
  *     value whose hash sort fails the lane-order guard (pmc_ctx_guard_counts counts[0]; never seen on
- *     gfx950), which the retry kernel redoes at level 9.  Decompress is the same at both levels.
+ *     gfx950), which the retry kernel redoes at level 9.
+ *   PMC_LEVEL_FAST_ALL (2): the fast level for values of every size.
+ *     Values of at most 16382 bytes: exactly PMC_LEVEL_FAST's member, byte for byte -- with a
+ *     dictionary set, the same dictionary members (see "preset dictionary": whatever is said there of
+ *     the fast level holds for this one, for values of that size).
+ *     Values above 16382 bytes: a SEGMENTED FAST MEMBER.  The value is cut into segments of 2048
+ *     bytes, and each is parsed by the fast level's match finder behind the 2048 bytes that precede
+ *     it in the value (the first segment behind nothing): matches end at their segment's end and reach
+ *     at most 4095 bytes back (tests/fast_large_model.py is the normative statement; DESIGN.md §4
+ *     "Front, fast level, large values").  The output is one valid gzip member of one or more DEFLATE
+ *     blocks (16383 symbols each, a stored block where that is smaller), at most pmc_gzip_bound(len)
+ *     bytes, header bytes 4..7 = 0 -- never a dictionary member, with or without a dictionary set --
+ *     and header byte 8 = 4, that any inflate decodes to the input.  It is NOT the reference's bytes.
+ *     A member depends on the value only: not on the entry point, the batch size, the batch position
+ *     or the other values of the batch (neither the one-kernel latency path nor the batch-dependent
+ *     shortcut for lone 16-32 KB values is taken at this level).  A value one of whose segments fails
+ *     the lane-order guard is redone at level 9 by the retry kernel (header byte 8 = 2), as above.
+ * PMC_LEVEL_EXACT and PMC_LEVEL_FAST do not change by a bit for having the third beside them.
+ * Decompress is the same at every level.
  * pmc_ctx_set_level takes effect for the calls issued after it returns; stores and slabs compress
  * through their context and follow it.  Any other level, or a NULL context, gives PMC_E_ARG (no device
- * is touched); so does PMC_LEVEL_FAST on a context whose create-time lane-order probe failed (its
- * level stays 9).  pmc_group_set_level sets every member context, or none.
- * The environment variable PMC_LEVEL (fast / 1, exact / 9) sets the initial level of every context
+ * is touched); so does PMC_LEVEL_FAST or PMC_LEVEL_FAST_ALL on a context whose create-time lane-order
+ * probe failed (its level stays 9).  pmc_group_set_level sets every member context, or none.
+ * The environment variable PMC_LEVEL (fast / 1, fast-all / 2, exact / 9) sets the initial level of every context
  * created afterwards, the default context -- hence the drop-in GzipCompressor and the servers --
  * included; unset means exact. */
 #define PMC_LEVEL_EXACT 9
 #define PMC_LEVEL_FAST 1
+#define PMC_LEVEL_FAST_ALL 2
 int pmc_ctx_set_level(pmc_ctx *ctx, int level);
 int pmc_ctx_get_level(pmc_ctx *ctx, int *level);
 

@@ -168,6 +168,9 @@ struct HostBuf {
 
 using namespace pmc;
 
+// the levels whose values of <= 16382 bytes take the fast front (PMC_LEVEL_FAST_ALL: the longer ones too)
+static inline bool level_is_fast(int level) { return level == PMC_LEVEL_FAST || level == PMC_LEVEL_FAST_ALL; }
+
 struct pmc_ctx {
     int device = 0;
     int cus = 0;
@@ -185,7 +188,8 @@ struct pmc_ctx {
     DevBuf guard;
     DevBuf rlist;                // compress: the per-call retry list (DeflateArgs::rlist)
     bool lane_order_ok = true;
-    // compression level of the calls issued from now on (pmc_ctx_set_level): PMC_LEVEL_EXACT or PMC_LEVEL_FAST
+    // compression level of the calls issued from now on (pmc_ctx_set_level): PMC_LEVEL_EXACT, PMC_LEVEL_FAST
+    // or PMC_LEVEL_FAST_ALL
     std::atomic<int> level{PMC_LEVEL_EXACT};
     // preset dictionary (pmc_ctx_set_dictionary): its bytes on the device (zero padded to a multiple of 16),
     // length and id (CRC-32; 0 = none).  Written with host_mu and both dir_mu held, read under a dir_mu.
@@ -354,6 +358,7 @@ static int env_level() {
     const char *e = getenv("PMC_LEVEL");
     if (!e) return PMC_LEVEL_EXACT;
     if (!strcmp(e, "fast") || !strcmp(e, "1")) return PMC_LEVEL_FAST;
+    if (!strcmp(e, "fast-all") || !strcmp(e, "2")) return PMC_LEVEL_FAST_ALL;
     if (!strcmp(e, "exact") || !strcmp(e, "9")) return PMC_LEVEL_EXACT;
     return -1;
 }
@@ -366,7 +371,7 @@ PMC_API int pmc_ctx_create(int device, pmc_ctx **out) {
     *out = nullptr;
     const int lvl = env_level();
     if (lvl < 0) {
-        g_err = std::string("PMC_LEVEL=") + getenv("PMC_LEVEL") + ": expected fast, 1, exact or 9";
+        g_err = std::string("PMC_LEVEL=") + getenv("PMC_LEVEL") + ": expected fast, 1, fast-all, 2, exact or 9";
         return PMC_E_ARG;
     }
     std::vector<uint8_t> env_dict; // PMC_DICT: checked before any device is touched, as PMC_LEVEL
@@ -399,6 +404,8 @@ PMC_API int pmc_ctx_create(int device, pmc_ctx **out) {
         HIP_TRY(hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
     HIP_TRY(hipFuncSetAttribute((const void *)deflate_front_fast_dict_kernel,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu));
+    HIP_TRY(hipFuncSetAttribute((const void *)lv_fast_parse_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)kLdsPerCu));
     HIP_TRY(hipFuncSetAttribute((const void *)deflate_back_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)kLdsPerCu));
     HIP_TRY(hipFuncSetAttribute((const void *)deflate_trees_kernel<kTreesCap1K>,
@@ -438,11 +445,11 @@ PMC_API int pmc_ctx_create(int device, pmc_ctx **out) {
         return PMC_E_NO_DEVICE;
     }
     c->lane_order_ok = probe == 0;
-    if (lvl == PMC_LEVEL_FAST) {
-        // (the fast front shares the sort whose lane order the probe just checked: a context that failed it
+    if (level_is_fast(lvl)) {
+        // (the fast fronts share the sort whose lane order the probe just checked: a context that failed it
         // stays exact, as pmc_ctx_set_level would answer)
-        if (c->lane_order_ok) c->level = PMC_LEVEL_FAST;
-        else g_err = "PMC_LEVEL=fast ignored: the lane-order probe failed, the context stays at level 9";
+        if (c->lane_order_ok) c->level = lvl;
+        else g_err = "PMC_LEVEL=fast / fast-all ignored: the lane-order probe failed, the context stays at level 9";
     }
     if (!env_dict.empty()) {
         rc = set_dictionary_locked(c, env_dict.data(), env_dict.size(), host_crc32(env_dict.data(), env_dict.size()));
@@ -456,8 +463,8 @@ PMC_API int pmc_ctx_create(int device, pmc_ctx **out) {
 }
 
 PMC_API int pmc_ctx_set_level(pmc_ctx *ctx, int level) {
-    if (!ctx || (level != PMC_LEVEL_EXACT && level != PMC_LEVEL_FAST)) return PMC_E_ARG;
-    if (level == PMC_LEVEL_FAST && !ctx->lane_order_ok) return PMC_E_ARG;
+    if (!ctx || (level != PMC_LEVEL_EXACT && !level_is_fast(level))) return PMC_E_ARG;
+    if (level_is_fast(level) && !ctx->lane_order_ok) return PMC_E_ARG;
     ctx->level = level;
     return PMC_OK;
 }
@@ -806,6 +813,7 @@ static int large_values(pmc_ctx *ctx, const DeflateArgs &a, uint64_t lo, uint64_
         L.map = (uint32_t *)(d + b_map);
         L.seg_tok = (uint32_t *)(d + b_stok);
         L.fail = (int32_t *)(d + b_fail);
+        L.xfl = 2; // (exact members: the reference's header)
         const unsigned cb = (unsigned)std::min<uint64_t>((nch + 3) / 4, (uint64_t)ctx->cus * 8);
         const unsigned sb = (unsigned)std::min<uint64_t>((nseg + 3) / 4, (uint64_t)ctx->cus * 8);
         const unsigned vb = (unsigned)std::min<uint64_t>(nv, (uint64_t)ctx->cus * 4);
@@ -835,6 +843,123 @@ static int large_values(pmc_ctx *ctx, const DeflateArgs &a, uint64_t lo, uint64_
         hipError_t err = hipGetLastError();
         if (err != hipSuccess) {
             set_err("large-value kernels", err);
+            return PMC_E_NO_DEVICE;
+        }
+        v0 = v1;
+    }
+    return PMC_OK;
+}
+
+// The same values at PMC_LEVEL_FAST_ALL (pmc_deflate_fast_large.hip): the select kernel and its small
+// readback as above (the same synchronous step), then rounds of values whose segment token buffers (a
+// segment has at most as many tokens as bytes: 4 bytes of tokens per byte of value) and tables fit the
+// scratch budget.  No sort, rank, map or stitch scratch: one wave per segment parses it in LDS, and the
+// large-value emit kernel writes the members (header byte 8 = 4).
+static int large_values_fast(pmc_ctx *ctx, const DeflateArgs &a, uint64_t lo, uint64_t hi, hipStream_t st) {
+    const uint64_t n = a.n;
+    int r = ctx->lvsel.ensure(8 + 8 * n);
+    if (r) return r;
+    uint32_t *sel = (uint32_t *)ctx->lvsel.p;
+    HIP_TRY(hipMemsetAsync(sel, 0, 8, st));
+    hipLaunchKernelGGL(lv_select_kernel, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 4096)), dim3(256), 0, st,
+                       a.src_len, n, lo, hi, sel);
+    uint32_t cnt = 0;
+    HIP_TRY(hipMemcpyAsync(&cnt, sel, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (!cnt) return PMC_OK;
+    std::vector<uint32_t> list(2 * (size_t)cnt);
+    HIP_TRY(hipMemcpy(list.data(), sel + 2, 8 * (size_t)cnt, hipMemcpyDeviceToHost));
+    std::vector<std::pair<uint32_t, uint32_t>> vals(cnt);
+    for (uint32_t k = 0; k < cnt; k++) vals[k] = {list[2 * k], list[2 * k + 1]};
+    std::sort(vals.begin(), vals.end());
+    auto nseg_of = [](uint64_t len) { return (len + kFlSeg - 1) / kFlSeg; };
+    auto bytes_of = [&](uint64_t len) { return 4 * len + nseg_of(len) * 32 + 64; };
+    auto al = [](uint64_t x) { return (x + 255) & ~(uint64_t)255; };
+    const uint64_t budget = 24ull << 30;
+    const uint64_t fwb = lv_fast_wave_bytes();
+    const Launch Lp = plan_lds(ctx, (const void *)lv_fast_parse_kernel, fwb, 1ull << 40, 0);
+    size_t v0 = 0;
+    while (v0 < vals.size()) {
+        // one round: values v0 .. v1 - 1
+        size_t v1 = v0;
+        uint64_t need = 0, nseg = 0, maxlen = 0;
+        while (v1 < vals.size() && (v1 == v0 || need + bytes_of(vals[v1].second) <= budget)) {
+            const uint64_t len = vals[v1].second;
+            need += bytes_of(len);
+            nseg += nseg_of(len);
+            maxlen = std::max(maxlen, len);
+            v1++;
+        }
+        const uint32_t nv = (uint32_t)(v1 - v0);
+        // host tables, in the order of the device table buffer
+        const uint64_t o_val = 0, o_seg0 = al(o_val + 4ull * nv), o_sval = al(o_seg0 + 4ull * (nv + 1)),
+                       o_stok = al(o_sval + 4 * nseg), tab_bytes = al(o_stok + 8 * nseg);
+        HIP_TRY(hipStreamSynchronize(st)); // (the previous round's kernels read the pinned tables' device copy)
+        r = ctx->lvpin.ensure(tab_bytes);
+        if (!r) r = ctx->lvtab.ensure(tab_bytes);
+        if (r) return r;
+        uint8_t *h = (uint8_t *)ctx->lvpin.p;
+        uint32_t *t_val = (uint32_t *)(h + o_val), *t_seg0 = (uint32_t *)(h + o_seg0), *t_sval = (uint32_t *)(h + o_sval);
+        uint64_t *t_stok = (uint64_t *)(h + o_stok);
+        uint64_t tb = 0;
+        uint32_t sg = 0;
+        for (uint32_t ov = 0; ov < nv; ov++) {
+            const uint64_t len = vals[v0 + ov].second, ns = nseg_of(len);
+            t_val[ov] = vals[v0 + ov].first;
+            t_seg0[ov] = sg;
+            for (uint64_t j = 0; j < ns; j++, sg++) {
+                t_sval[sg] = ov;
+                t_stok[sg] = tb;
+                tb += std::min<uint64_t>(kFlSeg, len - j * kFlSeg);
+            }
+        }
+        t_seg0[nv] = sg;
+        uint8_t *dt = (uint8_t *)ctx->lvtab.p;
+        HIP_TRY(hipMemcpyAsync(dt, h, tab_bytes, hipMemcpyHostToDevice, st));
+        // round scratch: tok | seg_tok | fail
+        const uint64_t b_tok = 0, b_stok = al(b_tok + 4 * tb), b_fail = al(b_stok + 16 * nseg),
+                       scratch = al(b_fail + 4ull * nv);
+        r = ctx->lvbuf.ensure(scratch);
+        if (r) return r;
+        uint8_t *d = (uint8_t *)ctx->lvbuf.p;
+        LargeArgs L{};
+        L.src = a.src;
+        L.src_off = a.src_off;
+        L.src_len = a.src_len;
+        L.lv_val = (const uint32_t *)(dt + o_val);
+        L.lv_seg0 = (const uint32_t *)(dt + o_seg0);
+        L.seg_val = (const uint32_t *)(dt + o_sval);
+        L.seg_tok0 = (const uint64_t *)(dt + o_stok);
+        L.nv = nv;
+        L.nseg = (uint32_t)nseg;
+        L.tok = (uint32_t *)(d + b_tok);
+        L.seg_tok = (uint32_t *)(d + b_stok);
+        L.fail = (int32_t *)(d + b_fail);
+        L.xfl = 4; // gzip XFL: zlib's "fastest algorithm", as the small fast members
+        HIP_TRY(hipMemsetAsync(L.fail, 0, 4ull * nv, st));
+        DeflateArgs p = a;
+        p.cap_len = kFlCap;
+        p.wave_bytes = fwb;
+        klaunch(ctx, PMC_K_DEFLATE_LARGE, st, [&] {
+            const dim3 pg((unsigned)std::min<uint64_t>(Lp.blocks, (nseg + Lp.wpb - 1) / Lp.wpb));
+            hipLaunchKernelGGL(lv_fast_parse_kernel, pg, dim3(64 * Lp.wpb), Lp.lds, st, p, L);
+        });
+        // emit: one wave per value
+        DeflateArgs e = a;
+        e.cap_len = maxlen;
+        e.wave_bytes = deflate_lv_emit_wave_bytes(maxlen);
+        const uint64_t ew = std::max<uint64_t>(4, std::min<uint64_t>(
+            {(uint64_t)(nv + 3) / 4 * 4, (uint64_t)ctx->cus * 4, std::max<uint64_t>(4, (8ull << 30) / e.wave_bytes / 4 * 4)}));
+        r = ctx->lvemit.ensure(ew * e.wave_bytes);
+        if (r) return r;
+        e.scratch = (uint8_t *)ctx->lvemit.p;
+        klaunch(ctx, PMC_K_DEFLATE_LARGE_EMIT, st, [&] {
+            hipLaunchKernelGGL(deflate_lv_emit_kernel, dim3((unsigned)(ew / 4)), dim3(256), deflate_lv_emit_lds(4), st, e,
+                               L);
+        });
+        hipError_t err = hipGetLastError();
+        if (err != hipSuccess) {
+            set_err("fast large-value kernels", err);
             return PMC_E_NO_DEVICE;
         }
         v0 = v1;
@@ -875,7 +1000,11 @@ static int compress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t 
     // Fast level: every value of <= 16382 bytes goes through the split pipeline with the fast front, whatever
     // the batch (so a value's member does not depend on the entry point); longer values take the paths below
     // unchanged.  (PMC_DEFLATE_V1, the A/B safety net, stays exact.)
-    const bool fast = ctx->level == PMC_LEVEL_FAST && ctx->lane_order_ok && !force_v1;
+    // PMC_LEVEL_FAST_ALL: the same for values of <= 16382 bytes; every longer value goes to large_values_fast
+    // (segments through the fast front), so the batch-dependent large pass below is off.
+    const int level = ctx->level;
+    const bool fast = level_is_fast(level) && ctx->lane_order_ok && !force_v1;
+    const bool fast_all = fast && level == PMC_LEVEL_FAST_ALL;
     // With a dictionary (fast level only): values of D + len <= 16382 take the dictionary front, a pass of
     // its own by length; longer ones the plain fast front (a second pass) or the exact paths, as without one.
     const uint32_t dD = fast && ctx->dict_id ? ctx->dict_len : 0u;
@@ -899,7 +1028,7 @@ static int compress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t 
     // values above small_lim there).  PMC_BIG_PASS=1 / 0 forces it on / off.
     static const int big_env = getenv("PMC_BIG_PASS") ? atoi(getenv("PMC_BIG_PASS")) : -1;
     const bool big_pick = big_env >= 0 ? big_env != 0 : n <= 2 * (uint64_t)ctx->cus && max_len <= big_lim;
-    const bool big_pass = split && big_pick && max_len > small_lim && big_lim > small_lim;
+    const bool big_pass = split && !fast_all && big_pick && max_len > small_lim && big_lim > small_lim;
     const uint64_t big_hi = big_pass ? std::min<uint64_t>(big_lim, max_len) : 0;
     const uint64_t big_cap = big_pass ? std::min<uint64_t>((big_hi + 63) & ~(uint64_t)63, big_lim) : 0;
     const uint64_t hbm_cut = big_pass ? big_hi : lds_cut; // the HBM kernel takes lengths above this
@@ -1140,7 +1269,7 @@ static int compress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t 
     a.tokens = (uint32_t *)ctx->tokens.p;
     // ---- large values (> hbm_cut): segment-parallel parse, stitched, emitted per value ----
     if (lv) {
-        const int r = large_values(ctx, a, hbm_cut, max_len, st);
+        const int r = fast_all ? large_values_fast(ctx, a, hbm_cut, max_len, st) : large_values(ctx, a, hbm_cut, max_len, st);
         if (r) return r;
     }
     // ---- HBM kernel (V1: values > lds_cut; else gated retries) ----
@@ -1583,7 +1712,7 @@ int host_batch_locked(pmc_ctx *ctx, Dir dir, const uint8_t *src, const uint64_t 
     // round 5 measured the wave kernel still 2x ahead there).
     const uint64_t lat_max = latency_max_len(), lat_batch = latency_batch();
     // (a fast-level compress always takes the pipeline: the one-kernel path is exact only)
-    const bool fast = dir == kCompress && ctx->level == PMC_LEVEL_FAST && ctx->lane_order_ok;
+    const bool fast = dir == kCompress && level_is_fast(ctx->level) && ctx->lane_order_ok;
     const bool latency = !force_pipeline && (dir == kCompress ? !fast && n <= lat_batch && max_len <= lat_max
                                                               : latency_decompress(n, max_len, out_bytes));
     ctx->path_calls[(latency ? 0 : 2) + (dir == kCompress ? 0 : 1)]++;

@@ -399,7 +399,7 @@ struct DeflateWave {
         sync();
         if (l < 10) {
             const uint8_t hdr[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 2, 3};
-            outb[l] = hdr[l];
+            outb[l] = l == 8 ? (uint8_t)L.xfl : hdr[l];
         }
         sync();
         uint64_t bitpos = 80, pos = 0, block_start = 0, last_start = 0;

@@ -159,8 +159,9 @@ struct FastWave {
     }
 
     // (p0: the walk's first position -- 0, or the dictionary's length when `len` bytes of dictionary ||
-    // value are staged; literal tokens are stored relative to p0, in the value's coordinates)
-    template <int PK>
+    // value are staged; literal tokens are stored relative to p0, in the value's coordinates.  LITB: a
+    // literal token is the byte itself, the form the large-value emit reads -- pmc_deflate_fast_large.hip)
+    template <int PK, bool LITB = false>
     __device__ __forceinline__ uint32_t walk(uint32_t len, uint32_t p0 = 0) {
         const uint32_t l = (uint32_t)lane_id();
         uint32_t p = p0, ntok = 0;
@@ -202,16 +203,17 @@ struct FastWave {
             }
             p = w0 + pp;
             const uint64_t starts = (~0ull << pp0) & ballot(in) & ~cov;
-            if ((starts >> l) & 1ull) w.tok[ntok + popc_lt(starts)] = ism ? (x - q) << 16 | (mlen - 3u) : x - p0;
+            if ((starts >> l) & 1ull)
+                w.tok[ntok + popc_lt(starts)] = ism ? (x - q) << 16 | (mlen - 3u) : LITB ? (uint32_t)w.b[x] : x - p0;
             ntok += (uint32_t)__builtin_popcountll(starts);
         }
         return ntok;
     }
 
-    template <int PK>
+    template <int PK, bool LITB = false>
     __device__ __forceinline__ uint32_t parse(uint32_t npos, uint32_t len, uint32_t p0 = 0) {
         if (sflag(table<PK>(npos, len))) return kNtokRetry;
-        return walk<PK>(len, p0);
+        return walk<PK, LITB>(len, p0);
     }
 
     // (inlined into the kernel: called through a pointer, the SmallWave would live in scratch memory)

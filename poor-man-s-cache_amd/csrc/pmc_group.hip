@@ -93,8 +93,8 @@ PMC_API void pmc_group_destroy(pmc_group *g) {
 PMC_API int pmc_group_size(pmc_group *g) { return g ? (int)g->ctx.size() : 0; }
 
 PMC_API int pmc_group_set_level(pmc_group *g, int level) {
-    if (!g || (level != PMC_LEVEL_EXACT && level != PMC_LEVEL_FAST)) return PMC_E_ARG;
-    if (level == PMC_LEVEL_FAST) // (all members or none)
+    if (!g || (level != PMC_LEVEL_EXACT && !level_is_fast(level))) return PMC_E_ARG;
+    if (level_is_fast(level)) // (all members or none)
         for (auto *c : g->ctx)
             if (!c->lane_order_ok) return PMC_E_ARG;
     for (auto *c : g->ctx) c->level = level;

@@ -116,6 +116,7 @@ struct LargeArgs {
     uint32_t *map;            // [nseg][2][kLvOverlap]: loop-top states of the start / continuation regions
     uint32_t *seg_tok;        // [nseg][4]: tokens parsed, stitched begin, stitched end, (unused)
     int32_t *fail;            // [nv] no convergence at some boundary: the HBM kernel redoes the value
+    uint32_t xfl;             // gzip header byte 8 the emit writes: 2 for an exact member, 4 for a segmented fast one
 };
 __global__ void lv_select_kernel(const uint32_t *src_len, uint64_t n, uint64_t lo, uint64_t hi, uint32_t *out);
 __global__ void lv_sort_hist_kernel(LargeArgs a, int pass);
@@ -124,6 +125,10 @@ __global__ void lv_sort_scatter_kernel(LargeArgs a, int pass);
 __global__ void lv_rank_kernel(LargeArgs a);
 __global__ void lv_parse_kernel(LargeArgs a);
 __global__ void lv_stitch_kernel(LargeArgs a);
+// the fast parse of large values (pmc_deflate_fast_large.hip, PMC_LEVEL_FAST_ALL): one wave per segment fills
+// seg_tok / tok / fail from the fast front's parse; of the tables it reads lv_val, lv_seg0, seg_val, seg_tok0
+__global__ void lv_fast_parse_kernel(DeflateArgs a, LargeArgs L);
+uint64_t lv_fast_wave_bytes();
 
 constexpr int32_t kDeflateRetry = -7778;     // internal rc: the split pipeline declined the value
 constexpr uint32_t kNtokMultiBlock = 0xffffffffu; // cN marker: >= 16383 symbols

@@ -101,7 +101,7 @@ SIGNATURES = {
 }
 
 # compression levels (include/pmc_codec.h PMC_LEVEL_*)
-LEVEL_EXACT, LEVEL_FAST = 9, 1
+LEVEL_EXACT, LEVEL_FAST, LEVEL_FAST_ALL = 9, 1, 2
 # the longest preset dictionary (include/pmc_codec.h PMC_DICT_MAX)
 DICT_MAX = 8192
 
@@ -190,8 +190,9 @@ class Context:
 
     @property
     def level(self) -> int:
-        """LEVEL_EXACT (9: the reference's bytes) or LEVEL_FAST (1: a valid gzip member from the fast
-        parse, values <= 16382 B); include/pmc_codec.h "compression level".  Setting it takes effect
+        """LEVEL_EXACT (9: the reference's bytes), LEVEL_FAST (1: a valid gzip member from the fast
+        parse, values <= 16382 B) or LEVEL_FAST_ALL (2: the same, and segmented fast members for longer
+        values); include/pmc_codec.h "compression level".  Setting it takes effect
         for the calls issued afterwards."""
         v = _c.c_int(0)
         rc = lib().pmc_ctx_get_level(self.handle, ctypes.byref(v))
