@@ -168,9 +168,6 @@ struct HostBuf {
 
 using namespace pmc;
 
-// the levels whose values of <= 16382 bytes take the fast front (PMC_LEVEL_FAST_ALL: the longer ones too)
-static inline bool level_is_fast(int level) { return level == PMC_LEVEL_FAST || level == PMC_LEVEL_FAST_ALL; }
-
 struct pmc_ctx {
     int device = 0;
     int cus = 0;
@@ -702,12 +699,38 @@ static bool latency_decompress(uint64_t n, uint64_t max_out, uint64_t out_bytes)
     return n <= lb && max_out <= latency_max_out() && (max_out <= lm || out_bytes <= lb * lm);
 }
 
-// ---- large values (pmc_deflate_large.hip) ------------------------------------------------------------
+// ---- kernel instances ----------------------------------------------------------------------------------
+// Each is chosen once, as a typed pointer: the same pointer feeds the occupancy plan and the launch.
+using DeflateKernel = void (*)(DeflateArgs);
+using InflateKernel = void (*)(InflateArgs);
+// the split pipeline's front of a pass (fcap: front_cap_class(pcap); the dictionary front has one instance)
+static DeflateKernel front_kernel(bool dictp, bool fastp, uint32_t fcap) {
+    if (dictp) return deflate_front_fast_dict_kernel;
+    if (fastp)
+        return fcap == 1024 ? deflate_front_fast_kernel<1024>
+               : fcap == 4096 ? deflate_front_fast_kernel<4096> : deflate_front_fast_kernel<0>;
+    return fcap == 1024 ? deflate_front_kernel<1024> : fcap == 4096 ? deflate_front_kernel<4096> : deflate_front_kernel<0>;
+}
+// the one-kernel paths: the general LDS kernel (PMC_DEFLATE_V1) or the small kernel
+static DeflateKernel mono_kernel(bool v1) { return v1 ? deflate_kernel<false> : deflate_small_kernel; }
+// the record kernel's 1 KiB image instance, or the 4 KiB one
+static InflateKernel rec_kernel(bool out1k) { return out1k ? inflate_rec_kernel<1024> : inflate_rec_kernel<kRecOutMax>; }
+// the wave-per-member kernels (LDS / HBM working set), of a context with or without a dictionary
+static InflateKernel wave_kernel(bool hbm, bool dict) {
+    if (hbm) return dict ? inflate_dict_kernel<true> : inflate_kernel<true>;
+    return dict ? inflate_dict_kernel<false> : inflate_kernel<false>;
+}
+
+// ---- large values (pmc_deflate_large.hip, pmc_deflate_fast_large.hip) ------------------------------------
 // The batch's values of lo < len <= hi.  Their lengths live on the device: one small readback (a count,
-// then the (index, length) list) lets the host plan rounds of values whose sort arrays, token buffers
-// and state maps fit a scratch budget.  This is the only synchronous step of a device-resident compress
+// then the (index, length) list) lets the host plan rounds of values whose tables and scratch fit a
+// budget (LvRound, pmc_plan.hpp).  This is the only synchronous step of a device-resident compress
 // call, taken only when max_len says such values may be present.
-static int large_values(pmc_ctx *ctx, const DeflateArgs &a, uint64_t lo, uint64_t hi, hipStream_t st) {
+// Exact level: each round sorts the values' positions, parses segments speculatively and stitches them.
+// fast (PMC_LEVEL_FAST_ALL): no sort, rank, map or stitch scratch -- one wave per segment parses it in LDS.
+// Either way the large-value emit kernel then writes the members (header byte 8 = 2 / 4).
+// The loop body depends on the round only through its plan.
+static int large_values(pmc_ctx *ctx, const DeflateArgs &a, uint64_t lo, uint64_t hi, bool fast, hipStream_t st) {
     const uint64_t n = a.n;
     int r = ctx->lvsel.ensure(8 + 8 * n);
     if (r) return r;
@@ -724,115 +747,77 @@ static int large_values(pmc_ctx *ctx, const DeflateArgs &a, uint64_t lo, uint64_
     std::vector<std::pair<uint32_t, uint32_t>> vals(cnt);
     for (uint32_t k = 0; k < cnt; k++) vals[k] = {list[2 * k], list[2 * k + 1]};
     std::sort(vals.begin(), vals.end());
-    auto nseg_of = [](uint64_t len) { return std::max<uint64_t>(1, len / kLvSeg); };
-    auto nch_of = [](uint64_t len) { return (len - 2 + kLvChunk - 1) / kLvChunk; };
-    auto tok_of = [&](uint64_t len) { // token capacity of the value's segments
-        const uint64_t ns = nseg_of(len);
-        return (ns - 1) * (kLvSeg + kLvOverlap + 2) + (len - (ns - 1) * kLvSeg) + 2;
-    };
-    auto bytes_of = [&](uint64_t len) {
-        return 13 * (len - 2) + 4 * tok_of(len) + nseg_of(len) * (2 * kLvOverlap * 4 + 16) + nch_of(len) * 1024 + 64;
-    };
-    auto al = [](uint64_t x) { return (x + 255) & ~(uint64_t)255; };
     const uint64_t budget = 24ull << 30;
-    size_t v0 = 0;
-    while (v0 < vals.size()) {
-        // one round: values v0 .. v1 - 1
-        size_t v1 = v0;
-        uint64_t need = 0, P = 0, nseg = 0, nch = 0, maxlen = 0;
-        while (v1 < vals.size() && (v1 == v0 || need + bytes_of(vals[v1].second) <= budget)) {
-            const uint64_t len = vals[v1].second;
-            need += bytes_of(len);
-            P += len - 2;
-            nseg += nseg_of(len);
-            nch += nch_of(len);
-            maxlen = std::max(maxlen, len);
-            v1++;
-        }
-        const uint32_t nv = (uint32_t)(v1 - v0);
-        // host tables, in the order of the device table buffer
-        const uint64_t o_val = 0, o_pb = al(o_val + 4ull * nv), o_seg0 = al(o_pb + 8ull * nv),
-                       o_ch0 = al(o_seg0 + 4ull * (nv + 1)), o_sval = al(o_ch0 + 4ull * (nv + 1)),
-                       o_stok = al(o_sval + 4 * nseg), o_cval = al(o_stok + 8 * nseg), tab_bytes = al(o_cval + 4 * nch);
+    const uint64_t fwb = fast ? lv_fast_wave_bytes() : 0;
+    const Launch Lp = fast ? plan_lds(ctx, (const void *)lv_fast_parse_kernel, fwb, 1ull << 40, 0) : Launch{};
+    for (size_t v0 = 0; v0 < vals.size();) {
+        const LvRound R = lv_plan_round(vals.data(), vals.size(), v0, fast ? kFlSeg : 0u, budget);
         HIP_TRY(hipStreamSynchronize(st)); // (the previous round's kernels read the pinned tables' device copy)
-        r = ctx->lvpin.ensure(tab_bytes);
-        if (!r) r = ctx->lvtab.ensure(tab_bytes);
+        r = ctx->lvpin.ensure(R.tab_bytes);
+        if (!r) r = ctx->lvtab.ensure(R.tab_bytes);
         if (r) return r;
-        uint8_t *h = (uint8_t *)ctx->lvpin.p;
-        uint32_t *t_val = (uint32_t *)(h + o_val), *t_seg0 = (uint32_t *)(h + o_seg0), *t_ch0 = (uint32_t *)(h + o_ch0),
-                 *t_sval = (uint32_t *)(h + o_sval), *t_cval = (uint32_t *)(h + o_cval);
-        uint64_t *t_pb = (uint64_t *)(h + o_pb), *t_stok = (uint64_t *)(h + o_stok);
-        uint64_t pb = 0, tb = 0;
-        uint32_t sg = 0, ch = 0;
-        for (uint32_t ov = 0; ov < nv; ov++) {
-            const uint64_t len = vals[v0 + ov].second, ns = nseg_of(len), nc = nch_of(len);
-            t_val[ov] = vals[v0 + ov].first;
-            t_pb[ov] = pb;
-            t_seg0[ov] = sg;
-            t_ch0[ov] = ch;
-            for (uint64_t j = 0; j < ns; j++, sg++) {
-                t_sval[sg] = ov;
-                t_stok[sg] = tb;
-                tb += j + 1 < ns ? kLvSeg + kLvOverlap + 2 : len - j * kLvSeg + 2;
-            }
-            for (uint64_t c = 0; c < nc; c++, ch++) t_cval[ch] = ov;
-            pb += len - 2;
-        }
-        t_seg0[nv] = sg;
-        t_ch0[nv] = ch;
+        R.fill((uint8_t *)ctx->lvpin.p);
         uint8_t *dt = (uint8_t *)ctx->lvtab.p;
-        HIP_TRY(hipMemcpyAsync(dt, h, tab_bytes, hipMemcpyHostToDevice, st));
-        // round scratch: tmp | S | R | HC | hist | tok | map | seg_tok | fail
-        const uint64_t b_tmp = 0, b_S = al(b_tmp + 4 * P), b_R = al(b_S + 4 * P), b_HC = al(b_R + 4 * P),
-                       b_hist = al(b_HC + P), b_tok = al(b_hist + 1024 * nch), b_map = al(b_tok + 4 * tb),
-                       b_stok = al(b_map + 2ull * kLvOverlap * 4 * nseg), b_fail = al(b_stok + 16 * nseg),
-                       scratch = al(b_fail + 4ull * nv);
-        r = ctx->lvbuf.ensure(scratch);
+        HIP_TRY(hipMemcpyAsync(dt, ctx->lvpin.p, R.tab_bytes, hipMemcpyHostToDevice, st));
+        r = ctx->lvbuf.ensure(R.scratch_bytes);
         if (r) return r;
         uint8_t *d = (uint8_t *)ctx->lvbuf.p;
         LargeArgs L{};
         L.src = a.src;
         L.src_off = a.src_off;
         L.src_len = a.src_len;
-        L.lv_val = (const uint32_t *)(dt + o_val);
-        L.lv_pbase = (const uint64_t *)(dt + o_pb);
-        L.lv_seg0 = (const uint32_t *)(dt + o_seg0);
-        L.lv_ch0 = (const uint32_t *)(dt + o_ch0);
-        L.seg_val = (const uint32_t *)(dt + o_sval);
-        L.seg_tok0 = (const uint64_t *)(dt + o_stok);
-        L.ch_val = (const uint32_t *)(dt + o_cval);
-        L.nv = nv;
-        L.nseg = (uint32_t)nseg;
-        L.nch = (uint32_t)nch;
-        L.tmp = (uint32_t *)(d + b_tmp);
-        L.S = (uint32_t *)(d + b_S);
-        L.R = (uint32_t *)(d + b_R);
-        L.HC = d + b_HC;
-        L.hist = (uint32_t *)(d + b_hist);
-        L.tok = (uint32_t *)(d + b_tok);
-        L.map = (uint32_t *)(d + b_map);
-        L.seg_tok = (uint32_t *)(d + b_stok);
-        L.fail = (int32_t *)(d + b_fail);
-        L.xfl = 2; // (exact members: the reference's header)
-        const unsigned cb = (unsigned)std::min<uint64_t>((nch + 3) / 4, (uint64_t)ctx->cus * 8);
-        const unsigned sb = (unsigned)std::min<uint64_t>((nseg + 3) / 4, (uint64_t)ctx->cus * 8);
-        const unsigned vb = (unsigned)std::min<uint64_t>(nv, (uint64_t)ctx->cus * 4);
-        klaunch(ctx, PMC_K_DEFLATE_LARGE, st, [&] {
-            for (int pass = 0; pass < 2; pass++) {
-                hipLaunchKernelGGL(lv_sort_hist_kernel, dim3(cb), dim3(256), 0, st, L, pass);
-                hipLaunchKernelGGL(lv_sort_scan_kernel, dim3(vb), dim3(256), 0, st, L);
-                hipLaunchKernelGGL(lv_sort_scatter_kernel, dim3(cb), dim3(256), 0, st, L, pass);
-            }
-            hipLaunchKernelGGL(lv_rank_kernel, dim3(cb), dim3(256), 0, st, L);
-            hipLaunchKernelGGL(lv_parse_kernel, dim3(sb), dim3(256), 0, st, L);
-            hipLaunchKernelGGL(lv_stitch_kernel, dim3(vb), dim3(64), 0, st, L);
-        });
+        L.lv_val = (const uint32_t *)(dt + R.o_val);
+        L.lv_pbase = (const uint64_t *)(dt + R.o_pbase);
+        L.lv_seg0 = (const uint32_t *)(dt + R.o_seg0);
+        L.lv_ch0 = (const uint32_t *)(dt + R.o_ch0);
+        L.seg_val = (const uint32_t *)(dt + R.o_seg_val);
+        L.seg_tok0 = (const uint64_t *)(dt + R.o_seg_tok0);
+        L.ch_val = (const uint32_t *)(dt + R.o_ch_val);
+        L.nv = R.nv;
+        L.nseg = (uint32_t)R.nseg;
+        L.nch = (uint32_t)R.nch;
+        L.tmp = (uint32_t *)(d + R.b_tmp);
+        L.S = (uint32_t *)(d + R.b_S);
+        L.R = (uint32_t *)(d + R.b_R);
+        L.HC = d + R.b_HC;
+        L.hist = (uint32_t *)(d + R.b_hist);
+        L.tok = (uint32_t *)(d + R.b_tok);
+        L.map = (uint32_t *)(d + R.b_map);
+        L.seg_tok = (uint32_t *)(d + R.b_seg_tok);
+        L.fail = (int32_t *)(d + R.b_fail);
+        // gzip XFL: the reference's header for an exact member; zlib's "fastest algorithm" for a fast one, as
+        // the small fast members
+        L.xfl = fast ? 4 : 2;
+        if (fast) {
+            HIP_TRY(hipMemsetAsync(L.fail, 0, 4ull * R.nv, st));
+            DeflateArgs p = a;
+            p.cap_len = kFlCap;
+            p.wave_bytes = fwb;
+            klaunch(ctx, PMC_K_DEFLATE_LARGE, st, [&] {
+                const dim3 pg((unsigned)std::min<uint64_t>(Lp.blocks, (R.nseg + Lp.wpb - 1) / Lp.wpb));
+                hipLaunchKernelGGL(lv_fast_parse_kernel, pg, dim3(64 * Lp.wpb), Lp.lds, st, p, L);
+            });
+        } else {
+            const unsigned cb = (unsigned)std::min<uint64_t>((R.nch + 3) / 4, (uint64_t)ctx->cus * 8);
+            const unsigned sb = (unsigned)std::min<uint64_t>((R.nseg + 3) / 4, (uint64_t)ctx->cus * 8);
+            const unsigned vb = (unsigned)std::min<uint64_t>(R.nv, (uint64_t)ctx->cus * 4);
+            klaunch(ctx, PMC_K_DEFLATE_LARGE, st, [&] {
+                for (int pass = 0; pass < 2; pass++) {
+                    hipLaunchKernelGGL(lv_sort_hist_kernel, dim3(cb), dim3(256), 0, st, L, pass);
+                    hipLaunchKernelGGL(lv_sort_scan_kernel, dim3(vb), dim3(256), 0, st, L);
+                    hipLaunchKernelGGL(lv_sort_scatter_kernel, dim3(cb), dim3(256), 0, st, L, pass);
+                }
+                hipLaunchKernelGGL(lv_rank_kernel, dim3(cb), dim3(256), 0, st, L);
+                hipLaunchKernelGGL(lv_parse_kernel, dim3(sb), dim3(256), 0, st, L);
+                hipLaunchKernelGGL(lv_stitch_kernel, dim3(vb), dim3(64), 0, st, L);
+            });
+        }
         // emit: one wave per value
         DeflateArgs e = a;
-        e.cap_len = maxlen;
-        e.wave_bytes = deflate_lv_emit_wave_bytes(maxlen);
+        e.cap_len = R.maxlen;
+        e.wave_bytes = deflate_lv_emit_wave_bytes(R.maxlen);
         const uint64_t ew = std::max<uint64_t>(4, std::min<uint64_t>(
-            {(uint64_t)(nv + 3) / 4 * 4, (uint64_t)ctx->cus * 4, std::max<uint64_t>(4, (8ull << 30) / e.wave_bytes / 4 * 4)}));
+            {(uint64_t)(R.nv + 3) / 4 * 4, (uint64_t)ctx->cus * 4, std::max<uint64_t>(4, (8ull << 30) / e.wave_bytes / 4 * 4)}));
         r = ctx->lvemit.ensure(ew * e.wave_bytes);
         if (r) return r;
         e.scratch = (uint8_t *)ctx->lvemit.p;
@@ -842,131 +827,122 @@ static int large_values(pmc_ctx *ctx, const DeflateArgs &a, uint64_t lo, uint64_
         });
         hipError_t err = hipGetLastError();
         if (err != hipSuccess) {
-            set_err("large-value kernels", err);
+            set_err(fast ? "fast large-value kernels" : "large-value kernels", err);
             return PMC_E_NO_DEVICE;
         }
-        v0 = v1;
+        v0 = R.v1;
     }
     return PMC_OK;
 }
 
-// The same values at PMC_LEVEL_FAST_ALL (pmc_deflate_fast_large.hip): the select kernel and its small
-// readback as above (the same synchronous step), then rounds of values whose segment token buffers (a
-// segment has at most as many tokens as bytes: 4 bytes of tokens per byte of value) and tables fit the
-// scratch budget.  No sort, rank, map or stitch scratch: one wave per segment parses it in LDS, and the
-// large-value emit kernel writes the members (header byte 8 = 4).
-static int large_values_fast(pmc_ctx *ctx, const DeflateArgs &a, uint64_t lo, uint64_t hi, hipStream_t st) {
-    const uint64_t n = a.n;
-    int r = ctx->lvsel.ensure(8 + 8 * n);
-    if (r) return r;
-    uint32_t *sel = (uint32_t *)ctx->lvsel.p;
-    HIP_TRY(hipMemsetAsync(sel, 0, 8, st));
-    hipLaunchKernelGGL(lv_select_kernel, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 4096)), dim3(256), 0, st,
-                       a.src_len, n, lo, hi, sel);
-    uint32_t cnt = 0;
-    HIP_TRY(hipMemcpyAsync(&cnt, sel, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (!cnt) return PMC_OK;
-    std::vector<uint32_t> list(2 * (size_t)cnt);
-    HIP_TRY(hipMemcpy(list.data(), sel + 2, 8 * (size_t)cnt, hipMemcpyDeviceToHost));
-    std::vector<std::pair<uint32_t, uint32_t>> vals(cnt);
-    for (uint32_t k = 0; k < cnt; k++) vals[k] = {list[2 * k], list[2 * k + 1]};
-    std::sort(vals.begin(), vals.end());
-    auto nseg_of = [](uint64_t len) { return (len + kFlSeg - 1) / kFlSeg; };
-    auto bytes_of = [&](uint64_t len) { return 4 * len + nseg_of(len) * 32 + 64; };
-    auto al = [](uint64_t x) { return (x + 255) & ~(uint64_t)255; };
-    const uint64_t budget = 24ull << 30;
-    const uint64_t fwb = lv_fast_wave_bytes();
-    const Launch Lp = plan_lds(ctx, (const void *)lv_fast_parse_kernel, fwb, 1ull << 40, 0);
-    size_t v0 = 0;
-    while (v0 < vals.size()) {
-        // one round: values v0 .. v1 - 1
-        size_t v1 = v0;
-        uint64_t need = 0, nseg = 0, maxlen = 0;
-        while (v1 < vals.size() && (v1 == v0 || need + bytes_of(vals[v1].second) <= budget)) {
-            const uint64_t len = vals[v1].second;
-            need += bytes_of(len);
-            nseg += nseg_of(len);
-            maxlen = std::max(maxlen, len);
-            v1++;
-        }
-        const uint32_t nv = (uint32_t)(v1 - v0);
-        // host tables, in the order of the device table buffer
-        const uint64_t o_val = 0, o_seg0 = al(o_val + 4ull * nv), o_sval = al(o_seg0 + 4ull * (nv + 1)),
-                       o_stok = al(o_sval + 4 * nseg), tab_bytes = al(o_stok + 8 * nseg);
-        HIP_TRY(hipStreamSynchronize(st)); // (the previous round's kernels read the pinned tables' device copy)
-        r = ctx->lvpin.ensure(tab_bytes);
-        if (!r) r = ctx->lvtab.ensure(tab_bytes);
-        if (r) return r;
-        uint8_t *h = (uint8_t *)ctx->lvpin.p;
-        uint32_t *t_val = (uint32_t *)(h + o_val), *t_seg0 = (uint32_t *)(h + o_seg0), *t_sval = (uint32_t *)(h + o_sval);
-        uint64_t *t_stok = (uint64_t *)(h + o_stok);
-        uint64_t tb = 0;
-        uint32_t sg = 0;
-        for (uint32_t ov = 0; ov < nv; ov++) {
-            const uint64_t len = vals[v0 + ov].second, ns = nseg_of(len);
-            t_val[ov] = vals[v0 + ov].first;
-            t_seg0[ov] = sg;
-            for (uint64_t j = 0; j < ns; j++, sg++) {
-                t_sval[sg] = ov;
-                t_stok[sg] = tb;
-                tb += std::min<uint64_t>(kFlSeg, len - j * kFlSeg);
-            }
-        }
-        t_seg0[nv] = sg;
-        uint8_t *dt = (uint8_t *)ctx->lvtab.p;
-        HIP_TRY(hipMemcpyAsync(dt, h, tab_bytes, hipMemcpyHostToDevice, st));
-        // round scratch: tok | seg_tok | fail
-        const uint64_t b_tok = 0, b_stok = al(b_tok + 4 * tb), b_fail = al(b_stok + 16 * nseg),
-                       scratch = al(b_fail + 4ull * nv);
-        r = ctx->lvbuf.ensure(scratch);
-        if (r) return r;
-        uint8_t *d = (uint8_t *)ctx->lvbuf.p;
-        LargeArgs L{};
-        L.src = a.src;
-        L.src_off = a.src_off;
-        L.src_len = a.src_len;
-        L.lv_val = (const uint32_t *)(dt + o_val);
-        L.lv_seg0 = (const uint32_t *)(dt + o_seg0);
-        L.seg_val = (const uint32_t *)(dt + o_sval);
-        L.seg_tok0 = (const uint64_t *)(dt + o_stok);
-        L.nv = nv;
-        L.nseg = (uint32_t)nseg;
-        L.tok = (uint32_t *)(d + b_tok);
-        L.seg_tok = (uint32_t *)(d + b_stok);
-        L.fail = (int32_t *)(d + b_fail);
-        L.xfl = 4; // gzip XFL: zlib's "fastest algorithm", as the small fast members
-        HIP_TRY(hipMemsetAsync(L.fail, 0, 4ull * nv, st));
-        DeflateArgs p = a;
-        p.cap_len = kFlCap;
-        p.wave_bytes = fwb;
-        klaunch(ctx, PMC_K_DEFLATE_LARGE, st, [&] {
-            const dim3 pg((unsigned)std::min<uint64_t>(Lp.blocks, (nseg + Lp.wpb - 1) / Lp.wpb));
-            hipLaunchKernelGGL(lv_fast_parse_kernel, pg, dim3(64 * Lp.wpb), Lp.lds, st, p, L);
+// chunk scratch budget (PMC_SPLIT_CHUNK_MB): 96 GiB of the 288 GiB holds 14M 1-KiB values, so the
+// 10M north-star batch is one front/trees/back launch set (~7 KB of chunk arrays per 1 KiB value,
+// allocated only as large as the batch needs).  Fewer, larger chunks mean fewer kernel tails:
+// 2 / 6 / 9 / 16 / 48 / 96 GiB measured -50 %, -2 %, -1 %, 0, +0.9 %, +1.2 % round trip (same box)
+static uint64_t split_chunk_budget() {
+    static const uint64_t budget = (getenv("PMC_SPLIT_CHUNK_MB") ? (uint64_t)atoll(getenv("PMC_SPLIT_CHUNK_MB"))
+                                                                 : 98304ull) << 20;
+    return budget;
+}
+
+// One pass of the split pipeline over the batch (SplitPass, pmc_plan.hpp), chunk by chunk: front, visit
+// order, trees, back.  dD: the context's dictionary length, for a dictionary pass.  ctx->split holds
+// SplitLayout(pcap, chunk).bytes().
+static int run_split_pass(pmc_ctx *ctx, DeflateArgs &a, const SplitPass &ps, uint32_t dD, hipStream_t st) {
+    const uint64_t n = a.n, pcap = ps.pcap;
+    const bool fastp = ps.fastp, dictp = ps.dictp;
+    static const bool no_order = getenv("PMC_TREES_ORDER") && !atoi(getenv("PMC_TREES_ORDER"));
+    // (the front keeps no CRC table in LDS: its grid is sized for the blocks that really fit)
+    const size_t tl_small = (size_t)(kTreesCap + 1) * 64 * 4, tl_1k = (size_t)(kTreesCap1K + 1) * 64 * 4;
+    const size_t tl_big = (size_t)(kLCodes + 1) * 64 * 4;
+    const uint32_t fcap = dictp ? 0u : front_cap_class(pcap);
+    const uint64_t dcap = std::min<uint64_t>(((uint64_t)dD + ps.hi + 63) & ~(uint64_t)63, kDictSpan);
+    const uint64_t fwb = dictp   ? deflate_front_fast_wave_bytes(dcap)
+                         : fastp ? deflate_front_fast_wave_bytes(fcap ? fcap : pcap)
+                                 : deflate_front_wave_bytes(fcap ? fcap : pcap);
+    const uint64_t bwb = deflate_back_wave_bytes(pcap);
+    a.dict = dictp ? (const uint8_t *)ctx->dict.p : nullptr;
+    a.dict_len = dictp ? dD : 0u;
+    a.front_cap = dictp ? (uint32_t)dcap : 0u;
+    a.mtime = dictp ? ctx->dict_id : 0u; // gzip MTIME: the dictionary's id marks a dictionary member
+    a.xfl = fastp ? 4u : 2u; // gzip XFL: zlib's "fastest algorithm" for a fast member
+    const DeflateKernel fk = front_kernel(dictp, fastp, fcap);
+    const Launch Lf = plan_lds(ctx, (const void *)fk, fwb, n, 0);
+    const Launch Lb = plan_lds(ctx, (const void *)deflate_back_kernel, bwb, n, kBackTabBytes);
+    const uint64_t chunk = split_chunk_of(n, split_chunk_budget(), pcap);
+    const SplitLayout SL(pcap, chunk);
+    uint8_t *p = (uint8_t *)ctx->split.p;
+    a.cT = (uint32_t *)(p + SL.cT);
+    a.cN = (uint32_t *)(p + SL.cN);
+    a.cP = (uint32_t *)(p + SL.cP);
+    a.cG = (uint32_t *)(p + SL.cG);
+    a.cH = (uint16_t *)(p + SL.cH);
+    a.cL = p + SL.cL;
+    a.cB = (uint32_t *)(p + SL.cB);
+    a.cC = (uint32_t *)(p + SL.cC);
+    a.cD = (uint32_t *)(p + SL.cD);
+    a.cZ = (uint32_t *)(p + SL.cZ);
+    uint32_t *ord = (uint32_t *)(p + SL.ord), *obins = (uint32_t *)(p + SL.obins);
+    a.cQ = (uint32_t *)(p + SL.cQ);
+    a.min_len = ps.lo;
+    a.lds_max_len = ps.hi;
+    a.cap_len = pcap;
+    // front work grabs: several values per grab for small values, whose parse is shorter than
+    // the counter's serialised grabs (10M x 256 B: 1 per grab 114 ms, 4 or 8: 51 ms; 1 KiB: 2 per
+    // grab -0.3 %, 4 the same)
+    a.front_batch = pcap <= 512 ? 4u : pcap <= 2048 ? 2u : 1u;
+    for (uint64_t first = 0; first < n; first += chunk) {
+        a.first = first;
+        a.count = std::min<uint64_t>(chunk, n - first);
+        const unsigned tb = (unsigned)((a.count + 63) / 64);
+        a.wave_bytes = fwb;
+        if (hipMemsetAsync(a.cQ, 0, 8, st) != hipSuccess) return PMC_E_NO_DEVICE;
+        klaunch(ctx, PMC_K_DEFLATE_FRONT, st, [&] { // (a fast front is timed as the front it stands in for)
+            const dim3 fg((unsigned)std::min<uint64_t>(Lf.blocks, (a.count + Lf.wpb - 1) / Lf.wpb));
+            hipLaunchKernelGGL(fk, fg, dim3(64 * Lf.wpb), Lf.lds, st, a);
         });
-        // emit: one wave per value
-        DeflateArgs e = a;
-        e.cap_len = maxlen;
-        e.wave_bytes = deflate_lv_emit_wave_bytes(maxlen);
-        const uint64_t ew = std::max<uint64_t>(4, std::min<uint64_t>(
-            {(uint64_t)(nv + 3) / 4 * 4, (uint64_t)ctx->cus * 4, std::max<uint64_t>(4, (8ull << 30) / e.wave_bytes / 4 * 4)}));
-        r = ctx->lvemit.ensure(ew * e.wave_bytes);
-        if (r) return r;
-        e.scratch = (uint8_t *)ctx->lvemit.p;
-        klaunch(ctx, PMC_K_DEFLATE_LARGE_EMIT, st, [&] {
-            hipLaunchKernelGGL(deflate_lv_emit_kernel, dim3((unsigned)(ew / 4)), dim3(256), deflate_lv_emit_lds(4), st, e,
-                               L);
-        });
-        hipError_t err = hipGetLastError();
-        if (err != hipSuccess) {
-            set_err("fast large-value kernels", err);
-            return PMC_E_NO_DEVICE;
+        if (hipMemsetAsync(a.cD + a.count, 0, 4, st) != hipSuccess) return PMC_E_NO_DEVICE;
+        // trees visit order by used literal/length symbols (PMC_TREES_ORDER=0: index order)
+        a.cO = nullptr;
+        if (!no_order && a.count >= 4096) {
+            if (hipMemsetAsync(obins, 0, kOrderBins * 4, st) != hipSuccess) return PMC_E_NO_DEVICE;
+            const unsigned ob = (unsigned)std::min<uint64_t>((a.count + 1023) / 1024, (uint64_t)ctx->cus * 4);
+            klaunch(ctx, PMC_K_ORDER, st, [&] {
+                hipLaunchKernelGGL(order_hist_kernel, dim3(ob), dim3(256), 0, st, (const uint32_t *)a.cZ, a.count, obins);
+                hipLaunchKernelGGL(order_scan_kernel, dim3(1), dim3(1024), 0, st, obins);
+                hipLaunchKernelGGL(order_scatter_kernel, dim3(ob), dim3(256), 0, st, (const uint32_t *)a.cZ, a.count,
+                                   obins, ord);
+            });
+            a.cO = ord;
         }
-        v0 = v1;
+        klaunch(ctx, PMC_K_DEFLATE_TREES, st, [&] {
+            if (pcap <= 1024) hipLaunchKernelGGL(deflate_trees_kernel<kTreesCap1K>, dim3(tb), dim3(64), tl_1k, st, a);
+            else hipLaunchKernelGGL(deflate_trees_kernel<kTreesCap>, dim3(tb), dim3(64), tl_small, st, a);
+            // (the overflow list's walker: its 73.5 KB heap column fits two one-wave blocks per CU)
+            hipLaunchKernelGGL(deflate_trees_kernel<kLCodes>, dim3(std::min<unsigned>(tb, 2u * (unsigned)ctx->cus)),
+                               dim3(64), tl_big, st, a);
+        });
+        a.wave_bytes = bwb;
+        a.back_nostage = pcap <= kNostageMaxLen ? 1u : 0u;
+        // the values' CRC-32 for the back (counted with the back: it is the back's work moved out)
+        if (a.back_nostage) klaunch(ctx, PMC_K_DEFLATE_BACK, st, [&] {
+            const unsigned cb = (unsigned)std::min<uint64_t>((a.count + 511) / 512, (uint64_t)ctx->cus * 4);
+            hipLaunchKernelGGL(crc32_batch_kernel, dim3(cb), dim3(512), 0, st, (const uint8_t *)a.src,
+                               (const uint64_t *)(a.src_off + a.first), (const uint32_t *)(a.src_len + a.first),
+                               a.count, a.cC);
+        });
+        klaunch(ctx, PMC_K_DEFLATE_BACK, st, [&] {
+            hipLaunchKernelGGL(deflate_back_kernel,
+                               dim3((unsigned)std::min<uint64_t>(Lb.blocks, (a.count + Lb.wpb - 1) / Lb.wpb)),
+                               dim3(64 * Lb.wpb), Lb.lds, st, a);
+        });
     }
     return PMC_OK;
 }
 
+// A compress call: route (plan_route, pmc_plan.hpp: which path claims which lengths, and why) -> the split
+// pipeline's passes or the one-kernel path -> large values -> the HBM kernel (V1: by length; else the gated
+// retry pass).
 static int compress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t *src_off, const uint32_t *src_len,
                                uint32_t n, uint8_t *dst, const uint64_t *dst_off, const uint32_t *dst_cap,
                                uint32_t *dst_len, int32_t *rc, uint32_t max_len, void *stream,
@@ -986,107 +962,40 @@ static int compress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t 
 #if defined(PMC_STAMPS) || defined(PMC_PHASE_STOP)
     if (const char *e = getenv("PMC_STOP_AFTER")) a.stop_after = atoi(e); // diagnostic builds only
 #endif
-    // Values <= small_lim (16382): the split pipeline's small pass; 16382 < len <= big_lim (~31.9K,
-    // the front's 160 KiB LDS; MAX_DIST caps it at 32506): its large pass; the rest -- and
-    // large-pass values of >= 16383 symbols, which need several DEFLATE blocks -- the general
-    // kernel with its working set in HBM (pmc_deflate.hip).  PMC_DEFLATE_V1=1 routes everything
-    // through the general kernels (A/B and safety net); PMC_DEFLATE_MONO=1 the single-kernel path.
     static const bool force_v1 = getenv("PMC_DEFLATE_V1") && atoi(getenv("PMC_DEFLATE_V1"));
     static const bool mono_env = getenv("PMC_DEFLATE_MONO") && atoi(getenv("PMC_DEFLATE_MONO"));
-    // (a context whose lane-order probe failed compresses through the single-kernel path, whose
-    // sort and codes use per-lane counters and ballots instead of returning-atomic ranks)
-    // (small: a device-resident batch within the latency path's limits -- the one-kernel path, as for
-    // host calls, but with the argument check and the retry pass of the device-resident API)
-    // Fast level: every value of <= 16382 bytes goes through the split pipeline with the fast front, whatever
-    // the batch (so a value's member does not depend on the entry point); longer values take the paths below
-    // unchanged.  (PMC_DEFLATE_V1, the A/B safety net, stays exact.)
-    // PMC_LEVEL_FAST_ALL: the same for values of <= 16382 bytes; every longer value goes to large_values_fast
-    // (segments through the fast front), so the batch-dependent large pass below is off.
-    const int level = ctx->level;
-    const bool fast = level_is_fast(level) && ctx->lane_order_ok && !force_v1;
-    const bool fast_all = fast && level == PMC_LEVEL_FAST_ALL;
-    // With a dictionary (fast level only): values of D + len <= 16382 take the dictionary front, a pass of
-    // its own by length; longer ones the plain fast front (a second pass) or the exact paths, as without one.
-    const uint32_t dD = fast && ctx->dict_id ? ctx->dict_len : 0u;
-    const bool mono = !fast && (mono_env || latency || small || !ctx->lane_order_ok);
-    const bool split = !force_v1 && !mono;
-    const uint64_t small_lim = force_v1 ? 0 : deflate_small_limit();
-    const uint64_t big_lim = split ? deflate_big_limit() : small_lim;
-    const uint64_t v1_lim = deflate_lds_limit();
-    const uint64_t lds_cut = force_v1 ? std::min<uint64_t>(v1_lim, std::max<uint64_t>(max_len, 1))
-                                      : std::min<uint64_t>(small_lim, std::max<uint64_t>(max_len, 1));
-    uint64_t cap = (lds_cut + 63) & ~(uint64_t)63;
-    cap = std::min<uint64_t>(cap, force_v1 ? v1_lim : small_lim);
-    // large pass: values in (small_lim, big_hi]
-    // The split pipeline's large pass (16382 < len <= ~31.8K through the front at one wave per CU, the
-    // front's working set filling the CU's LDS) is off since round 5: the large-value pipeline compresses
-    // these values 1.8x faster (100K x 30 KB: 1.55 -> 2.84 GiB/s, 500K x 20 KB 1.58 -> 3.07, same box,
-    // profiles/r05/large) -- except in small batches: one wave per value of the large pass finishes a
-    // lone 30 KB value in ~5 ms, the large-value pipeline's two 16 KiB segment parses (global-memory
-    // chains) in ~10 ms, so batches of up to 2 values per CU that hold no value above the large pass's
-    // limit keep it (a batch with longer values runs the large-value pipeline anyway and sends all its
-    // values above small_lim there).  PMC_BIG_PASS=1 / 0 forces it on / off.
     static const int big_env = getenv("PMC_BIG_PASS") ? atoi(getenv("PMC_BIG_PASS")) : -1;
-    const bool big_pick = big_env >= 0 ? big_env != 0 : n <= 2 * (uint64_t)ctx->cus && max_len <= big_lim;
-    const bool big_pass = split && !fast_all && big_pick && max_len > small_lim && big_lim > small_lim;
-    const uint64_t big_hi = big_pass ? std::min<uint64_t>(big_lim, max_len) : 0;
-    const uint64_t big_cap = big_pass ? std::min<uint64_t>((big_hi + 63) & ~(uint64_t)63, big_lim) : 0;
-    const uint64_t hbm_cut = big_pass ? big_hi : lds_cut; // the HBM kernel takes lengths above this
-    // values above hbm_cut: the large-value path (pmc_deflate_large.hip), except on the V1 A/B path
-    const bool lv = !force_v1 && max_len > hbm_cut;
-    uint64_t hbm_waves = 0, hbm_wb = deflate_wave_bytes(true, max_len);
-    // The HBM kernel takes values by length only on the V1 path.  Otherwise it runs gated, as the retry
-    // pass of the values this call's other paths declined (a lane-order guard fired, a large-pass value
-    // of several blocks, a large value whose segments did not stitch): it visits the call's retry list
-    // (DeflateArgs::rlist) and returns at once when the list is empty.  The latency path launches no
-    // retry pass: host_batch reads the verdicts and redoes a declined call through the pipeline.
-    const bool gated = !(force_v1 && max_len > hbm_cut);
-    if (!gated || !latency) {
-        // as many waves as the kernel's 196 VGPRs let a CU hold (2 per SIMD) within a scratch budget
-        // (32 GiB for the V1 path's length-routed values; 8 GiB for retries, whose waves exit at once
-        // when there are none): at 2 waves per CU (round 1-2) the latency-bound walk left 64 KiB values
-        // at 0.52 GiB/s, and a 64-wave retry pass left periodic 1 MiB values and multi-block 24 KB
-        // values 32x short of that
-        // A batch of single-block values (max_len <= kSmallMax) can have retries only from a lane-order
-        // guard, which never fired on gfx950 (and a context whose create-time probe sees the order broken
-        // sends every batch to the per-lane-counter kernels instead): 64 waves, and 64 waves' scratch,
-        // cover that.  Only batches with longer values (multi-block large-pass values, large values whose
-        // segments did not stitch) size the pass for throughput (the scratch a gated pass
-        // allocates stays with the context).
-        const uint64_t cap_waves = gated && max_len <= kSmallMax ? 64ull : (uint64_t)ctx->cus * 8;
-        hbm_waves = std::max<uint64_t>(1, std::min<uint64_t>(cap_waves,
-                                                             ((gated ? 8ull : 32ull) << 30) / std::max<uint64_t>(hbm_wb, 1)));
-    }
-    hbm_waves = std::min<uint64_t>(hbm_waves, n);
-    if (gated && hbm_waves) {
+    static const uint64_t small_lim = deflate_small_limit(), big_lim = deflate_big_limit(), v1_lim = deflate_lds_limit();
+    const uint64_t hbm_wb = deflate_wave_bytes(true, max_len);
+    RouteIn in{};
+    in.n = n;
+    in.max_len = max_len;
+    in.level = ctx->level;
+    in.lane_order_ok = ctx->lane_order_ok;
+    in.dict_len = ctx->dict_id ? ctx->dict_len : 0u;
+    in.cus = (uint64_t)ctx->cus;
+    in.latency = latency;
+    in.small = small;
+    in.force_v1 = force_v1;
+    in.mono_env = mono_env;
+    in.big_env = big_env;
+    in.small_lim = small_lim;
+    in.big_lim = big_lim;
+    in.v1_lim = v1_lim;
+    in.single_block_max = kSmallMax;
+    in.hbm_wb = hbm_wb;
+    const Route R = plan_route(in);
+    const uint64_t hbm_waves = R.hbm_waves;
+    if (R.rlist) {
         int r = ctx->rlist.ensure(4ull * ((uint64_t)n + 1));
         if (r) return r;
         HIP_TRY(hipMemsetAsync(ctx->rlist.p, 0, 4, st));
         a.rlist = (uint32_t *)ctx->rlist.p;
     }
-    if (split) {
-        // chunk scratch budget (PMC_SPLIT_CHUNK_MB): 96 GiB of the 288 GiB holds 14M 1-KiB values, so the
-        // 10M north-star batch is one front/trees/back launch set (~7 KB of chunk arrays per 1 KiB value,
-        // allocated only as large as the batch needs).  Fewer, larger chunks mean fewer kernel tails:
-        // 2 / 6 / 9 / 16 / 48 / 96 GiB measured -50 %, -2 %, -1 %, 0, +0.9 %, +1.2 % round trip (same box)
-        static const uint64_t budget = (getenv("PMC_SPLIT_CHUNK_MB") ? (uint64_t)atoll(getenv("PMC_SPLIT_CHUNK_MB"))
-                                                                     : 98304ull) << 20;
-        auto chunk_of = [&](uint64_t c) {
-            uint64_t ch = std::min<uint64_t>(n, std::max<uint64_t>(4096, budget / split_value_bytes(c)));
-            return (ch + 63) & ~(uint64_t)63;
-        };
-        auto scratch_of = [&](uint64_t c, uint64_t ch) {
-            const uint64_t blocks = ch / 64;
-            return ch * c * 4 + ch * 4 + ch * 4 + blocks * 64 * kSplitRows * 3 + blocks * 64 * kMergeRows * 4 +
-                   blocks * 64 * kHdrWords * 4 + ch * 4 +
-                   (ch + 1) * 4 + ch * 8 + kOrderBins * 4 + 64 + 1024;
-        };
-        uint64_t need = scratch_of(cap, chunk_of(cap));
-        // (the dictionary pass: its values' lengths and the cap of its token slabs and back)
-        const uint64_t dict_hi = dD ? std::min<uint64_t>(lds_cut, kDictSpan - dD) : 0;
-        const uint64_t dict_cap = std::min<uint64_t>(cap, (dict_hi + 63) & ~(uint64_t)63);
-        if (dD) need = std::max<uint64_t>(need, scratch_of(dict_cap, chunk_of(dict_cap)));
-        if (big_pass) need = std::max<uint64_t>(need, scratch_of(big_cap, chunk_of(big_cap)));
+    if (R.kind == Route::kSplit) {
+        uint64_t need = 0;
+        for (int k = 0; k < R.npass; k++)
+            need = std::max(need, SplitLayout(R.pass[k].pcap, split_chunk_of(n, split_chunk_budget(), R.pass[k].pcap)).bytes());
         int r = ctx->split.ensure(need);
         if (r) return r;
         if (hbm_waves) {
@@ -1095,140 +1004,10 @@ static int compress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t 
             r = ctx->dscratch.ensure(hbm_waves * hbm_wb);
             if (r) return r;
         }
-        static const bool no_order = getenv("PMC_TREES_ORDER") && !atoi(getenv("PMC_TREES_ORDER"));
-        // (the front keeps no CRC table in LDS: its grid is sized for the blocks that really fit)
-        const size_t tl_small = (size_t)(kTreesCap + 1) * 64 * 4, tl_1k = (size_t)(kTreesCap1K + 1) * 64 * 4;
-        const size_t tl_big = (size_t)(kLCodes + 1) * 64 * 4;
-        // one pass over the batch for the values with lo < len <= hi, working sets sized for pcap
-        // (dictp: the fast front behind the context's dictionary; its LDS layout follows D + hi, the token
-        // slabs, trees and back pcap as ever -- a value has at most len tokens)
-        auto run_pass = [&](uint64_t lo, uint64_t hi, uint64_t pcap, bool fastp, bool dictp) -> int {
-            const uint32_t fcap = dictp ? 0u : front_cap_class(pcap);
-            const uint64_t dcap = std::min<uint64_t>(((uint64_t)dD + hi + 63) & ~(uint64_t)63, kDictSpan);
-            const uint64_t fwb = dictp   ? deflate_front_fast_wave_bytes(dcap)
-                                 : fastp ? deflate_front_fast_wave_bytes(fcap ? fcap : pcap)
-                                         : deflate_front_wave_bytes(fcap ? fcap : pcap);
-            const uint64_t bwb = deflate_back_wave_bytes(pcap);
-            a.dict = dictp ? (const uint8_t *)ctx->dict.p : nullptr;
-            a.dict_len = dictp ? dD : 0u;
-            a.front_cap = dictp ? (uint32_t)dcap : 0u;
-            a.mtime = dictp ? ctx->dict_id : 0u; // gzip MTIME: the dictionary's id marks a dictionary member
-            const void *fk = dictp ? (const void *)deflate_front_fast_dict_kernel
-                             : fastp ? (fcap == 1024   ? (const void *)deflate_front_fast_kernel<1024>
-                                      : fcap == 4096 ? (const void *)deflate_front_fast_kernel<4096>
-                                                     : (const void *)deflate_front_fast_kernel<0>)
-                             : fcap == 1024 ? (const void *)deflate_front_kernel<1024>
-                             : fcap == 4096 ? (const void *)deflate_front_kernel<4096>
-                                            : (const void *)deflate_front_kernel<0>;
-            a.xfl = fastp ? 4u : 2u; // gzip XFL: zlib's "fastest algorithm" for a fast member
-            Launch Lf = plan_lds(ctx, fk, fwb, n, 0);
-            const size_t front_lds = Lf.lds;
-            Launch Lb = plan_lds(ctx, (const void *)deflate_back_kernel, bwb, n, kBackTabBytes);
-            const uint64_t chunk = chunk_of(pcap), blocks = chunk / 64;
-            uint8_t *p = (uint8_t *)ctx->split.p;
-            a.cT = (uint32_t *)p;
-            p += chunk * pcap * 4;
-            a.cN = (uint32_t *)p;
-            p += chunk * 4;
-            a.cP = (uint32_t *)p;
-            p += chunk * 4;
-            a.cG = (uint32_t *)p;
-            p += blocks * 64 * kMergeRows * 4;
-            a.cH = (uint16_t *)p;
-            p += blocks * 64 * kSplitRows * 2;
-            a.cL = (uint8_t *)p;
-            p += blocks * 64 * kSplitRows;
-            a.cB = (uint32_t *)p;
-            p += blocks * 64 * kHdrWords * 4;
-            a.cC = (uint32_t *)p;
-            p += chunk * 4;
-            a.cD = (uint32_t *)p;
-            p += (chunk + 1) * 4;
-            a.cZ = (uint32_t *)p;
-            p += chunk * 4;
-            uint32_t *ord = (uint32_t *)p;
-            p += chunk * 4;
-            uint32_t *obins = (uint32_t *)p;
-            p += kOrderBins * 4;
-            a.cQ = (uint32_t *)p;
-            a.min_len = lo;
-            a.lds_max_len = hi;
-            a.cap_len = pcap;
-            // front work grabs: several values per grab for small values, whose parse is shorter than
-            // the counter's serialised grabs (10M x 256 B: 1 per grab 114 ms, 4 or 8: 51 ms; 1 KiB: 2 per
-            // grab -0.3 %, 4 the same)
-            a.front_batch = pcap <= 512 ? 4u : pcap <= 2048 ? 2u : 1u;
-            for (uint64_t first = 0; first < n; first += chunk) {
-                a.first = first;
-                a.count = std::min<uint64_t>(chunk, n - first);
-                const unsigned tb = (unsigned)((a.count + 63) / 64);
-                a.wave_bytes = fwb;
-                if (hipMemsetAsync(a.cQ, 0, 8, st) != hipSuccess) return PMC_E_NO_DEVICE;
-                klaunch(ctx, PMC_K_DEFLATE_FRONT, st, [&] {
-                    const dim3 fg((unsigned)std::min<uint64_t>(Lf.blocks, (a.count + Lf.wpb - 1) / Lf.wpb));
-                    if (dictp) {
-                        hipLaunchKernelGGL(deflate_front_fast_dict_kernel, fg, dim3(64 * Lf.wpb), front_lds, st, a);
-                    } else if (fastp) { // (timed as the front it stands in for)
-                        if (fcap == 1024)
-                            hipLaunchKernelGGL(deflate_front_fast_kernel<1024>, fg, dim3(64 * Lf.wpb), front_lds, st, a);
-                        else if (fcap == 4096)
-                            hipLaunchKernelGGL(deflate_front_fast_kernel<4096>, fg, dim3(64 * Lf.wpb), front_lds, st, a);
-                        else
-                            hipLaunchKernelGGL(deflate_front_fast_kernel<0>, fg, dim3(64 * Lf.wpb), front_lds, st, a);
-                    } else if (fcap == 1024)
-                        hipLaunchKernelGGL(deflate_front_kernel<1024>, fg, dim3(64 * Lf.wpb), front_lds, st, a);
-                    else if (fcap == 4096)
-                        hipLaunchKernelGGL(deflate_front_kernel<4096>, fg, dim3(64 * Lf.wpb), front_lds, st, a);
-                    else
-                        hipLaunchKernelGGL(deflate_front_kernel<0>, fg, dim3(64 * Lf.wpb), front_lds, st, a);
-                });
-                if (hipMemsetAsync(a.cD + a.count, 0, 4, st) != hipSuccess) return PMC_E_NO_DEVICE;
-                // trees visit order by used literal/length symbols (PMC_TREES_ORDER=0: index order)
-                a.cO = nullptr;
-                if (!no_order && a.count >= 4096) {
-                    if (hipMemsetAsync(obins, 0, kOrderBins * 4, st) != hipSuccess) return PMC_E_NO_DEVICE;
-                    const unsigned ob = (unsigned)std::min<uint64_t>((a.count + 1023) / 1024, (uint64_t)ctx->cus * 4);
-                    klaunch(ctx, PMC_K_ORDER, st, [&] {
-                        hipLaunchKernelGGL(order_hist_kernel, dim3(ob), dim3(256), 0, st, (const uint32_t *)a.cZ,
-                                           a.count, obins);
-                        hipLaunchKernelGGL(order_scan_kernel, dim3(1), dim3(1024), 0, st, obins);
-                        hipLaunchKernelGGL(order_scatter_kernel, dim3(ob), dim3(256), 0, st, (const uint32_t *)a.cZ,
-                                           a.count, obins, ord);
-                    });
-                    a.cO = ord;
-                }
-                klaunch(ctx, PMC_K_DEFLATE_TREES, st, [&] {
-                    if (pcap <= 1024) hipLaunchKernelGGL(deflate_trees_kernel<kTreesCap1K>, dim3(tb), dim3(64), tl_1k, st, a);
-                    else hipLaunchKernelGGL(deflate_trees_kernel<kTreesCap>, dim3(tb), dim3(64), tl_small, st, a);
-                    // (the overflow list's walker: its 73.5 KB heap column fits two one-wave blocks per CU)
-                    hipLaunchKernelGGL(deflate_trees_kernel<kLCodes>, dim3(std::min<unsigned>(tb, 2u * (unsigned)ctx->cus)),
-                                       dim3(64), tl_big, st, a);
-                });
-                a.wave_bytes = bwb;
-                a.back_nostage = pcap <= kNostageMaxLen ? 1u : 0u;
-                // the values' CRC-32 for the back (counted with the back: it is the back's work moved out)
-                if (a.back_nostage) klaunch(ctx, PMC_K_DEFLATE_BACK, st, [&] {
-                    const unsigned cb = (unsigned)std::min<uint64_t>((a.count + 511) / 512, (uint64_t)ctx->cus * 4);
-                    hipLaunchKernelGGL(crc32_batch_kernel, dim3(cb), dim3(512), 0, st, (const uint8_t *)a.src,
-                                       (const uint64_t *)(a.src_off + a.first), (const uint32_t *)(a.src_len + a.first),
-                                       a.count, a.cC);
-                });
-                klaunch(ctx, PMC_K_DEFLATE_BACK, st, [&] {
-                    hipLaunchKernelGGL(deflate_back_kernel,
-                                       dim3((unsigned)std::min<uint64_t>(Lb.blocks, (a.count + Lb.wpb - 1) / Lb.wpb)),
-                                       dim3(64 * Lb.wpb), Lb.lds, st, a);
-                });
-            }
-            return PMC_OK;
-        };
-        if (dD) {
-            r = run_pass(0, dict_hi, dict_cap, true, true);
-            if (!r && lds_cut > dict_hi) r = run_pass(dict_hi, lds_cut, cap, true, false);
-        } else {
-            r = run_pass(0, lds_cut, cap, fast, false);
+        for (int k = 0; k < R.npass; k++) {
+            r = run_split_pass(ctx, a, R.pass[k], R.dict_len, st);
+            if (r) return r;
         }
-        if (!r && big_pass) r = run_pass(small_lim, big_hi, big_cap, false, false);
-        if (r) return r;
         a.min_len = 0;
         a.xfl = 2; // (everything after the small pass is exact)
         a.mtime = 0;
@@ -1238,9 +1017,10 @@ static int compress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t 
             return PMC_E_NO_DEVICE;
         }
     } else {
-        const void *lds_kernel = force_v1 ? (const void *)deflate_kernel<false> : (const void *)deflate_small_kernel;
-        const uint64_t lds_wb = force_v1 ? deflate_wave_bytes(false, cap) : deflate_small_wave_bytes(cap);
-        Launch Ls = plan_lds(ctx, lds_kernel, lds_wb, n);
+        const bool v1 = R.kind == Route::kV1;
+        const DeflateKernel lds_kernel = mono_kernel(v1);
+        const uint64_t lds_wb = v1 ? deflate_wave_bytes(false, R.cap) : deflate_small_wave_bytes(R.cap);
+        Launch Ls = plan_lds(ctx, (const void *)lds_kernel, lds_wb, n);
         const uint64_t small_waves = (uint64_t)Ls.blocks * Ls.wpb;
         // size every per-wave buffer before the first launch (no reallocation under a kernel)
         int r = ctx->tokens.ensure(std::max(small_waves, hbm_waves) * kSlabSyms * sizeof(uint32_t));
@@ -1252,14 +1032,12 @@ static int compress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t 
             if (r) return r;
         }
         a.tokens = (uint32_t *)ctx->tokens.p;
-        a.lds_max_len = lds_cut;
-        a.cap_len = cap;
+        a.lds_max_len = R.lds_cut;
+        a.cap_len = R.cap;
         a.wave_bytes = lds_wb;
         a.scratch = (uint8_t *)ctx->fbscratch.p;
-        klaunch(ctx, PMC_K_DEFLATE_MONO, st, [&] {
-            if (force_v1) hipLaunchKernelGGL(deflate_kernel<false>, dim3(Ls.blocks), dim3(64 * Ls.wpb), Ls.lds, st, a);
-            else hipLaunchKernelGGL(deflate_small_kernel, dim3(Ls.blocks), dim3(64 * Ls.wpb), Ls.lds, st, a);
-        });
+        klaunch(ctx, PMC_K_DEFLATE_MONO, st,
+                [&] { hipLaunchKernelGGL(lds_kernel, dim3(Ls.blocks), dim3(64 * Ls.wpb), Ls.lds, st, a); });
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) {
             set_err("deflate_kernel<lds>", e);
@@ -1268,16 +1046,16 @@ static int compress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t 
     }
     a.tokens = (uint32_t *)ctx->tokens.p;
     // ---- large values (> hbm_cut): segment-parallel parse, stitched, emitted per value ----
-    if (lv) {
-        const int r = fast_all ? large_values_fast(ctx, a, hbm_cut, max_len, st) : large_values(ctx, a, hbm_cut, max_len, st);
+    if (R.lv) {
+        const int r = large_values(ctx, a, R.hbm_cut, max_len, R.fast_all, st);
         if (r) return r;
     }
     // ---- HBM kernel (V1: values > lds_cut; else gated retries) ----
     if (hbm_waves) {
         a.cap_len = max_len;
-        a.lds_max_len = gated ? max_len : hbm_cut;
+        a.lds_max_len = R.gated ? max_len : R.hbm_cut;
         a.retry = 1; // (large-pass values of several blocks, and values a lane-order guard declined)
-        a.gate = gated ? 1 : 0;
+        a.gate = R.gated ? 1 : 0;
         a.wave_bytes = hbm_wb;
         a.scratch = (uint8_t *)ctx->dscratch.p;
         klaunch(ctx, PMC_K_DEFLATE_HBM, st, [&] {
@@ -1349,7 +1127,7 @@ static int decompress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_
             // the 1 KiB image instance when no member may decode to more (max_len: the largest capacity),
             // else the 4 KiB one
             const bool out1k = max_len <= 1024;
-            const void *rk = out1k ? (const void *)inflate_rec_kernel<1024> : (const void *)inflate_rec_kernel<kRecOutMax>;
+            const InflateKernel rk = rec_kernel(out1k);
             const uint32_t rlds = rec_lds_bytes(out1k ? 1024 : kRecOutMax);
             // exactly the resident blocks: a block owns its rows for the whole grid-stride loop,
             // and blocks beyond residency would start only when the first ones have finished
@@ -1357,7 +1135,7 @@ static int decompress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_
             int &rec_per_cu = rec_per_cu_k[out1k ? 1 : 0];
             if (!rec_per_cu) {
                 int nb = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rk, 64, rlds) != hipSuccess || nb < 1)
+                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)rk, 64, rlds) != hipSuccess || nb < 1)
                     nb = (int)(kLdsPerCu / rlds);
                 rec_per_cu = nb;
             }
@@ -1384,11 +1162,7 @@ static int decompress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_
 #if defined(PMC_STAMPS) || defined(PMC_PHASE_STOP)
             if (const char *e = getenv("PMC_STOP_AFTER")) a.stop_after = atoi(e); // 31 prepare, 32 phase A
 #endif
-            klaunch(ctx, PMC_K_INFLATE_REC, st,
-                    [&] {
-                        if (out1k) hipLaunchKernelGGL(inflate_rec_kernel<1024>, dim3(rb), dim3(64), rlds, st, a);
-                        else hipLaunchKernelGGL(inflate_rec_kernel<kRecOutMax>, dim3(rb), dim3(64), rlds, st, a);
-                    });
+            klaunch(ctx, PMC_K_INFLATE_REC, st, [&] { hipLaunchKernelGGL(rk, dim3(rb), dim3(64), rlds, st, a); });
             a.big_only = 1;
         }
         // members of several blocks exist only above 16383 output bytes (zlib flushes every 16383
@@ -1437,12 +1211,11 @@ static int decompress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_
     a.dict_last = dict_second ? 0u : 1u;
     {
         uint64_t wb = inflate_wave_bytes(false, a.dict_out, a.lds_max_in);
-        Launch L = plan_lds(ctx, dD ? (const void *)inflate_dict_kernel<false> : (const void *)inflate_kernel<false>, wb, n);
+        const InflateKernel lk = wave_kernel(false, dD != 0);
+        Launch L = plan_lds(ctx, (const void *)lk, wb, n);
         a.wave_bytes = wb;
-        klaunch(ctx, PMC_K_INFLATE_LDS, st, [&] {
-            if (dD) hipLaunchKernelGGL(inflate_dict_kernel<false>, dim3(L.blocks), dim3(64 * L.wpb), L.lds, st, a);
-            else hipLaunchKernelGGL(inflate_kernel<false>, dim3(L.blocks), dim3(64 * L.wpb), L.lds, st, a);
-        });
+        klaunch(ctx, PMC_K_INFLATE_LDS, st,
+                [&] { hipLaunchKernelGGL(lk, dim3(L.blocks), dim3(64 * L.wpb), L.lds, st, a); });
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) {
             set_err("inflate_kernel<lds>", e);
@@ -1459,10 +1232,10 @@ static int decompress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_
         a2.dict_out = (uint32_t)a2.lds_max_out;
         a2.lds_max_in = dict_in;
         a2.wave_bytes = inflate_wave_bytes(false, a2.dict_out, a2.lds_max_in);
-        Launch L = plan_lds(ctx, (const void *)inflate_dict_kernel<false>, a2.wave_bytes, n);
-        klaunch(ctx, PMC_K_INFLATE_LDS, st, [&] {
-            hipLaunchKernelGGL(inflate_dict_kernel<false>, dim3(L.blocks), dim3(64 * L.wpb), L.lds, st, a2);
-        });
+        const InflateKernel lk = wave_kernel(false, true);
+        Launch L = plan_lds(ctx, (const void *)lk, a2.wave_bytes, n);
+        klaunch(ctx, PMC_K_INFLATE_LDS, st,
+                [&] { hipLaunchKernelGGL(lk, dim3(L.blocks), dim3(64 * L.wpb), L.lds, st, a2); });
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) {
             set_err("inflate_dict_kernel<lds>", e);
@@ -1478,12 +1251,8 @@ static int decompress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_
         uint64_t waves = std::min<uint64_t>((uint64_t)ctx->cus * 4, n);
         a.wave_bytes = wb;
         klaunch(ctx, PMC_K_INFLATE_HBM, st, [&] {
-            if (dD)
-                hipLaunchKernelGGL(inflate_dict_kernel<true>, dim3((unsigned)((waves + 3) / 4)), dim3(256),
-                                   kCrcTabBytes + 4 * wb, st, a);
-            else
-                hipLaunchKernelGGL(inflate_kernel<true>, dim3((unsigned)((waves + 3) / 4)), dim3(256),
-                                   kCrcTabBytes + 4 * wb, st, a);
+            hipLaunchKernelGGL(wave_kernel(true, dD != 0), dim3((unsigned)((waves + 3) / 4)), dim3(256),
+                               kCrcTabBytes + 4 * wb, st, a);
         });
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) {

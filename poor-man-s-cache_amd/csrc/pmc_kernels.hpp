@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pmc_plan.hpp" // kLvSeg / kLvOverlap / kLvChunk, the chunk-array row counts, kOrderBins, kDictSpan
+
 namespace pmc {
 
 constexpr int PMC_INVALID_INPUT_DEV = -999;
@@ -95,7 +97,6 @@ __device__ inline void retry_push(const DeflateArgs &a, uint64_t v) {
 // (on through kLvOverlap positions of the next segment); a parse is exact from the first loop-top
 // position where its state equals the exact parse of the segment before it (stitching), and one wave
 // per value then emits the stitched token stream block by block (deflate_lv_emit_kernel).
-constexpr uint32_t kLvSeg = 16384, kLvOverlap = 2048, kLvChunk = 4096;
 struct LargeArgs {
     const uint8_t *src;
     const uint64_t *src_off;
@@ -135,11 +136,6 @@ constexpr uint32_t kNtokMultiBlock = 0xffffffffu; // cN marker: >= 16383 symbols
 constexpr uint32_t kNtokRetry = 0xfffffffeu;      // cN marker: the sort's lane-order guard fired (retry)
 
 constexpr uint32_t kBackTabBytes = 8 * 256 * 4; // the back kernel's slicing-by-8 CRC tables (LDS per block)
-constexpr uint32_t kSplitRows = 336;  // 286 lit/len + 30 dist + 19 bit-length (+1)
-constexpr uint32_t kMergeRows = 572;  // 2 heap entries per merge, <= 285 merges
-// a dynamic block's tree header (HLIT..send_tree, at most 14 + 19 * 3 + 316 * 7 = 2283 bits): word 0 the
-// bit count, then the bits LSB-first (76 words: 16-byte rows)
-constexpr uint32_t kHdrWords = 76;
 // For values of more than kHdrMinLen bytes the trees kernel (one lane per value) emits the header bits and
 // sets kPlanHdr in the plan; the back copies them.  (Same box, 10M x 1 KiB: trees 20.6 -> 27.8 ms, back
 // 36.7 -> 26.3; 1M x 4 KiB: -1.2 ms; at 256 B the trees' cost exceeded the back's saving, +6.8 / -5.4 ms,
@@ -162,11 +158,6 @@ constexpr int kTreesCap = PMC_TREES_CAP; // lane heap capacity of the first tree
 #define PMC_TREES_CAP1K 79
 #endif
 constexpr int kTreesCap1K = PMC_TREES_CAP1K;
-
-// bytes of chunk scratch per value of the split pipeline
-__host__ __device__ inline uint64_t split_value_bytes(uint64_t cap) {
-    return cap * 4 + 4 + kSplitRows * 2 + kSplitRows + 4 + kMergeRows * 4 + 4 + 8;
-}
 
 struct InflateArgs {
     const uint8_t *src;
@@ -222,12 +213,9 @@ __device__ inline bool dict_member(BytePtr m, uint32_t in_len, uint32_t id) {
     const uint32_t mt = m[4] | (uint32_t)m[5] << 8 | (uint32_t)m[6] << 16 | (uint32_t)m[7] << 24;
     return m[3] == 0 && m[8] == 4 && mt == id;
 }
-// the longest value a dictionary of D bytes is used for (D + len <= 16382)
-constexpr uint32_t kDictSpan = 16382;
 
-// lane-inflate visit order: member indices grouped by compressed length, so a wave's 64
+// lane-inflate visit order: member indices grouped by compressed length (kOrderBins bins), so a wave's 64
 // lanes decode members of similar length and finish their decode loops together
-constexpr uint32_t kOrderBins = 2048;
 __global__ void order_hist_kernel(const uint32_t *src_len, uint64_t n, uint32_t *hist);
 __global__ void order_scan_kernel(uint32_t *hist);
 __global__ void order_scatter_kernel(const uint32_t *src_len, uint64_t n, uint32_t *cursor, uint32_t *order);

@@ -1,0 +1,324 @@
+// pmc_plan.hpp -- the host-side planning arithmetic of a compress call: which path claims which lengths
+// (Route), where the split pipeline's chunk arrays lie (SplitLayout) and how the large values are cut
+// into rounds (LvRound).  Plain C++17 with no HIP in it: pmc_capi.hip turns these plans into launches,
+// and tests/host/plan_check.cpp prints them for tests/test_host_plan.py, which needs no GPU.
+#pragma once
+#include <stdint.h>
+
+#include <algorithm>
+#include <utility>
+#include <vector>
+
+#include "../../include/pmc_codec.h"
+
+namespace pmc {
+
+// ---- large-value rounds ------------------------------------------------------------------------------
+// exact level (pmc_deflate_large.hip): segments of kLvSeg positions, each parsed on through kLvOverlap
+// positions of the next; the hash sort works in chunks of kLvChunk positions
+constexpr uint32_t kLvSeg = 16384, kLvOverlap = 2048, kLvChunk = 4096;
+
+// One round of a call's large values: the values vals[v0 .. v1) whose tables and scratch fit the budget,
+// with the layout of the table buffer (host-filled, copied to the device) and of the round scratch.
+// Every region starts on a multiple of 256 bytes; a region of no elements takes no space, so the fast
+// level's rounds (no pbase / ch0 / ch_val tables, no sort scratch) are the same routine's.
+struct LvRound {
+    const std::pair<uint32_t, uint32_t> *vals; // the call's large values (batch index, length), sorted
+    uint32_t fast_seg;                         // 0: exact level; else the fast level's segment bytes
+    size_t v0, v1;
+    uint32_t nv;
+    uint64_t nseg, nch;  // segments, sort chunks (fast: none)
+    uint64_t P;          // positions, sum of len - 2 (fast: not counted, 0)
+    uint64_t tb;         // tokens the segment buffers hold
+    uint64_t maxlen;
+    // tables: val[nv] u32 | pbase[nv] u64 | seg0[nv + 1] u32 | ch0[nv + 1] u32 | seg_val[nseg] u32 |
+    // seg_tok0[nseg] u64 | ch_val[nch] u32
+    uint64_t o_val, o_pbase, o_seg0, o_ch0, o_seg_val, o_seg_tok0, o_ch_val, tab_bytes;
+    // scratch: tmp | S | R (4P each) | HC (P) | hist | tok | map | seg_tok | fail
+    uint64_t b_tmp, b_S, b_R, b_HC, b_hist, b_tok, b_map, b_seg_tok, b_fail, scratch_bytes;
+
+    bool exact() const { return fast_seg == 0; }
+    uint64_t nseg_of(uint64_t len) const {
+        return exact() ? std::max<uint64_t>(1, len / kLvSeg) : (len + fast_seg - 1) / fast_seg;
+    }
+    uint64_t nch_of(uint64_t len) const { return exact() ? (len - 2 + kLvChunk - 1) / kLvChunk : 0; }
+    // token capacity of the value's segment j: an exact segment may parse on through the overlap (+2: the
+    // positions without a hash); a fast segment has at most as many tokens as bytes
+    uint64_t seg_tok_cap(uint64_t len, uint64_t j) const {
+        if (exact()) return j + 1 < nseg_of(len) ? kLvSeg + kLvOverlap + 2 : len - j * kLvSeg + 2;
+        return std::min<uint64_t>(fast_seg, len - j * fast_seg);
+    }
+    uint64_t tok_of(uint64_t len) const { // the sum of seg_tok_cap over the value's segments
+        const uint64_t ns = nseg_of(len);
+        return exact() ? (ns - 1) * (kLvSeg + kLvOverlap + 2) + (len - (ns - 1) * kLvSeg) + 2 : len;
+    }
+    // what a value adds to a round's need: its sort arrays (13 bytes per position), token buffers, state
+    // maps, per-segment rows, histograms and table rows (fast: 4 bytes of tokens per byte, 32 per segment)
+    uint64_t cost(uint64_t len) const {
+        if (exact())
+            return 13 * (len - 2) + 4 * tok_of(len) + nseg_of(len) * (2 * kLvOverlap * 4 + 16) + nch_of(len) * 1024 + 64;
+        return 4 * len + nseg_of(len) * 32 + 64;
+    }
+
+    // Writes the tables at their offsets into `h` (tab_bytes bytes, 8-byte aligned).
+    void fill(uint8_t *h) const {
+        uint32_t *t_val = (uint32_t *)(h + o_val), *t_seg0 = (uint32_t *)(h + o_seg0), *t_ch0 = (uint32_t *)(h + o_ch0),
+                 *t_sval = (uint32_t *)(h + o_seg_val), *t_cval = (uint32_t *)(h + o_ch_val);
+        uint64_t *t_pb = (uint64_t *)(h + o_pbase), *t_stok = (uint64_t *)(h + o_seg_tok0);
+        uint64_t pb = 0, t = 0;
+        uint32_t sg = 0, ch = 0;
+        for (uint32_t ov = 0; ov < nv; ov++) {
+            const uint64_t len = vals[v0 + ov].second, ns = nseg_of(len), nc = nch_of(len);
+            t_val[ov] = vals[v0 + ov].first;
+            t_seg0[ov] = sg;
+            if (exact()) {
+                t_pb[ov] = pb;
+                t_ch0[ov] = ch;
+            }
+            for (uint64_t j = 0; j < ns; j++, sg++) {
+                t_sval[sg] = ov;
+                t_stok[sg] = t;
+                t += seg_tok_cap(len, j);
+            }
+            for (uint64_t c = 0; c < nc; c++, ch++) t_cval[ch] = ov;
+            pb += len - 2;
+        }
+        t_seg0[nv] = sg;
+        if (exact()) t_ch0[nv] = ch;
+    }
+};
+
+// The round that starts at vals[v0] (v0 < nvals): values are taken while need + cost <= budget, and the
+// first one always.  The next round starts at the returned v1.
+inline LvRound lv_plan_round(const std::pair<uint32_t, uint32_t> *vals, size_t nvals, size_t v0, uint32_t fast_seg,
+                             uint64_t budget) {
+    LvRound r{};
+    r.vals = vals;
+    r.fast_seg = fast_seg;
+    r.v0 = r.v1 = v0;
+    uint64_t need = 0;
+    while (r.v1 < nvals && (r.v1 == v0 || need + r.cost(vals[r.v1].second) <= budget)) {
+        const uint64_t len = vals[r.v1].second;
+        need += r.cost(len);
+        if (r.exact()) r.P += len - 2;
+        r.nseg += r.nseg_of(len);
+        r.nch += r.nch_of(len);
+        r.tb += r.tok_of(len);
+        r.maxlen = std::max(r.maxlen, len);
+        r.v1++;
+    }
+    r.nv = (uint32_t)(r.v1 - v0);
+    const uint64_t nv = r.nv, ex = r.exact() ? 1 : 0;
+    uint64_t o = 0;
+    auto region = [&o](uint64_t bytes) { // the region's offset; `o` moves to the next region's
+        const uint64_t at = o;
+        o = (o + bytes + 255) & ~(uint64_t)255;
+        return at;
+    };
+    r.o_val = region(4 * nv);
+    r.o_pbase = region(ex * 8 * nv);
+    r.o_seg0 = region(4 * (nv + 1));
+    r.o_ch0 = region(ex * 4 * (nv + 1));
+    r.o_seg_val = region(4 * r.nseg);
+    r.o_seg_tok0 = region(8 * r.nseg);
+    r.o_ch_val = region(4 * r.nch);
+    r.tab_bytes = o;
+    o = 0;
+    r.b_tmp = region(4 * r.P);
+    r.b_S = region(4 * r.P);
+    r.b_R = region(4 * r.P);
+    r.b_HC = region(r.P);
+    r.b_hist = region(1024 * r.nch);
+    r.b_tok = region(4 * r.tb);
+    r.b_map = region(ex * 2 * kLvOverlap * 4 * r.nseg);
+    r.b_seg_tok = region(16 * r.nseg);
+    r.b_fail = region(4 * nv);
+    r.scratch_bytes = o;
+    return r;
+}
+
+// ---- split pipeline chunk arrays (DeflateArgs cT .. cQ; pmc_deflate_split.hip) -------------------------
+constexpr uint32_t kSplitRows = 336;  // 286 lit/len + 30 dist + 19 bit-length (+1)
+constexpr uint32_t kMergeRows = 572;  // 2 heap entries per merge, <= 285 merges
+// a dynamic block's tree header (HLIT..send_tree, at most 14 + 19 * 3 + 316 * 7 = 2283 bits): word 0 the
+// bit count, then the bits LSB-first (76 words: 16-byte rows)
+constexpr uint32_t kHdrWords = 76;
+// lane-inflate / trees visit order: indices grouped into this many bins (by compressed length, so a
+// wave's 64 lanes decode members of similar length and finish their decode loops together; by used symbols)
+constexpr uint32_t kOrderBins = 2048;
+
+// The one statement of where a chunk's arrays lie in the context's split scratch: byte offsets for a
+// pass of cap `pcap` over chunks of `chunk` values (a multiple of 64).  The rows of cH / cL / cB / cG
+// are per value, `chunk` of them.  cB's 16-byte rows are aligned because every array before it is a
+// multiple of 16 bytes per 64 values.
+struct SplitLayout {
+    uint64_t cT, cN, cP, cG, cH, cL, cB, cC, cD, cZ, ord, obins, cQ;
+    SplitLayout(uint64_t pcap, uint64_t chunk) {
+        uint64_t o = 0;
+        auto array = [&o](uint64_t bytes) {
+            const uint64_t at = o;
+            o += bytes;
+            return at;
+        };
+        cT = array(chunk * pcap * 4);
+        cN = array(chunk * 4);
+        cP = array(chunk * 4);
+        cG = array(chunk * kMergeRows * 4);
+        cH = array(chunk * kSplitRows * 2);
+        cL = array(chunk * kSplitRows);
+        cB = array(chunk * kHdrWords * 4);
+        cC = array(chunk * 4);
+        cD = array((chunk + 1) * 4); // (+1: the number of deferred values)
+        cZ = array(chunk * 4);
+        ord = array(chunk * 4);
+        obins = array(kOrderBins * 4);
+        cQ = o; // the two work counters
+    }
+    // the scratch a pass needs: the arrays, cQ's 64 bytes and 1 KiB of slack
+    uint64_t bytes() const { return cQ + 64 + 1024; }
+};
+
+// What the chunk budget is divided by to get the values per chunk: the per-value arrays that dominated
+// when the budget was calibrated -- not the footprint (SplitLayout::bytes() is; it also holds cB, cC,
+// cZ and ord).  Chunk sizes are behaviour: tests/test_gpu_fullsize.py sizes its budgets by this.
+inline uint64_t split_value_bytes(uint64_t cap) {
+    return cap * 4 + 4 + kSplitRows * 2 + kSplitRows + 4 + kMergeRows * 4 + 4 + 8;
+}
+// values per chunk of a pass of cap `cap` over a batch of n (a multiple of 64, at least 4096 unless n is less)
+inline uint64_t split_chunk_of(uint64_t n, uint64_t budget, uint64_t cap) {
+    const uint64_t ch = std::min<uint64_t>(n, std::max<uint64_t>(4096, budget / split_value_bytes(cap)));
+    return (ch + 63) & ~(uint64_t)63;
+}
+
+// ---- the compress route ----------------------------------------------------------------------------------
+// the levels whose values of <= 16382 bytes take the fast front (PMC_LEVEL_FAST_ALL: the longer ones too)
+inline bool level_is_fast(int level) { return level == PMC_LEVEL_FAST || level == PMC_LEVEL_FAST_ALL; }
+
+// the longest value a dictionary of D bytes is used for (D + len <= 16382)
+constexpr uint32_t kDictSpan = 16382;
+
+struct RouteIn {
+    uint64_t n, max_len;  // values in the batch; the caller's bound on their lengths (>= 1)
+    int level;            // PMC_LEVEL_*
+    bool lane_order_ok;   // the context's create-time probe passed
+    uint32_t dict_len;    // the context's dictionary (0: none)
+    uint64_t cus;
+    bool latency, small;  // the host calls' latency path; a device-resident batch within its limits
+    bool force_v1, mono_env; // PMC_DEFLATE_V1, PMC_DEFLATE_MONO
+    int big_env;          // PMC_BIG_PASS: 1 / 0 forces the large pass on / off, -1 unset
+    // deflate_small_limit(), deflate_big_limit(), deflate_lds_limit() (they follow the kernels' LDS layouts)
+    uint64_t small_lim, big_lim, v1_lim;
+    uint64_t single_block_max; // kSmallMax: a longer value may need several DEFLATE blocks
+    uint64_t hbm_wb;           // the HBM kernel's working set per wave at max_len
+};
+
+// one pass of the split pipeline over the batch: the values with lo < len <= hi, working sets sized for
+// pcap (dictp: the fast front behind the context's dictionary; its LDS layout follows D + hi, the token
+// slabs, trees and back pcap as ever -- a value has at most len tokens)
+struct SplitPass {
+    uint64_t lo, hi, pcap;
+    bool fastp, dictp;
+};
+
+// Which path claims which lengths of (0, max_len].  kSplit: `pass[0 .. npass)`; kMono / kV1: one kernel
+// for (0, lds_cut] (deflate_small_kernel / deflate_kernel<false>).  Above hbm_cut: the large-value rounds
+// (lv), or on the V1 path the HBM kernel by length (!gated).  Otherwise the HBM kernel runs gated, as
+// the retry pass, with hbm_waves waves (0: no pass).
+struct Route {
+    enum Kind { kSplit, kMono, kV1 } kind;
+    SplitPass pass[3];
+    int npass;
+    uint64_t lds_cut, cap; // kMono / kV1: the kernel's longest value and its working-set cap
+    uint32_t dict_len;     // the dictionary the dictionary pass uses (0: no such pass)
+    bool lv, fast_all;     // large-value rounds run; at the fast level (large_values' mode)
+    uint64_t hbm_cut;
+    bool gated, rlist;     // rlist: the call needs a retry list (a gated pass will run)
+    uint64_t hbm_waves;
+};
+
+inline Route plan_route(const RouteIn &in) {
+    Route R{};
+    const uint64_t n = in.n, max_len = in.max_len;
+    const bool force_v1 = in.force_v1;
+    // Values <= small_lim (16382): the split pipeline's small pass; 16382 < len <= big_lim (~31.9K,
+    // the front's 160 KiB LDS; MAX_DIST caps it at 32506): its large pass; the rest -- and
+    // large-pass values of >= 16383 symbols, which need several DEFLATE blocks -- the general
+    // kernel with its working set in HBM (pmc_deflate.hip).  PMC_DEFLATE_V1=1 routes everything
+    // through the general kernels (A/B and safety net); PMC_DEFLATE_MONO=1 the single-kernel path.
+    // (a context whose lane-order probe failed compresses through the single-kernel path, whose
+    // sort and codes use per-lane counters and ballots instead of returning-atomic ranks)
+    // (small: a device-resident batch within the latency path's limits -- the one-kernel path, as for
+    // host calls, but with the argument check and the retry pass of the device-resident API)
+    // Fast level: every value of <= 16382 bytes goes through the split pipeline with the fast front, whatever
+    // the batch (so a value's member does not depend on the entry point); longer values take the paths below
+    // unchanged.  (PMC_DEFLATE_V1, the A/B safety net, stays exact.)
+    // PMC_LEVEL_FAST_ALL: the same for values of <= 16382 bytes; every longer value goes to the large-value
+    // rounds' fast mode (segments through the fast front), so the batch-dependent large pass below is off.
+    const bool fast = level_is_fast(in.level) && in.lane_order_ok && !force_v1;
+    R.fast_all = fast && in.level == PMC_LEVEL_FAST_ALL;
+    // With a dictionary (fast level only): values of D + len <= 16382 take the dictionary front, a pass of
+    // its own by length; longer ones the plain fast front (a second pass) or the exact paths, as without one.
+    R.dict_len = fast ? in.dict_len : 0u;
+    const bool mono = !fast && (in.mono_env || in.latency || in.small || !in.lane_order_ok);
+    const bool split = !force_v1 && !mono;
+    R.kind = split ? Route::kSplit : force_v1 ? Route::kV1 : Route::kMono;
+    const uint64_t small_lim = force_v1 ? 0 : in.small_lim;
+    const uint64_t big_lim = split ? in.big_lim : small_lim;
+    R.lds_cut = std::min<uint64_t>(force_v1 ? in.v1_lim : small_lim, std::max<uint64_t>(max_len, 1));
+    R.cap = std::min<uint64_t>((R.lds_cut + 63) & ~(uint64_t)63, force_v1 ? in.v1_lim : small_lim);
+    // large pass: values in (small_lim, big_hi]
+    // The split pipeline's large pass (16382 < len <= ~31.8K through the front at one wave per CU, the
+    // front's working set filling the CU's LDS) is off since round 5: the large-value pipeline compresses
+    // these values 1.8x faster (100K x 30 KB: 1.55 -> 2.84 GiB/s, 500K x 20 KB 1.58 -> 3.07, same box,
+    // profiles/r05/large) -- except in small batches: one wave per value of the large pass finishes a
+    // lone 30 KB value in ~5 ms, the large-value pipeline's two 16 KiB segment parses (global-memory
+    // chains) in ~10 ms, so batches of up to 2 values per CU that hold no value above the large pass's
+    // limit keep it (a batch with longer values runs the large-value pipeline anyway and sends all its
+    // values above small_lim there).  PMC_BIG_PASS=1 / 0 forces it on / off.
+    const bool big_pick = in.big_env >= 0 ? in.big_env != 0 : n <= 2 * in.cus && max_len <= big_lim;
+    const bool big_pass = split && !R.fast_all && big_pick && max_len > small_lim && big_lim > small_lim;
+    const uint64_t big_hi = big_pass ? std::min<uint64_t>(big_lim, max_len) : 0;
+    R.hbm_cut = big_pass ? big_hi : R.lds_cut; // the HBM kernel takes lengths above this
+    if (split) {
+        if (R.dict_len) {
+            // (the dictionary pass: its values' lengths and the cap of its token slabs and back)
+            const uint64_t dict_hi = std::min<uint64_t>(R.lds_cut, kDictSpan - R.dict_len);
+            R.pass[R.npass++] = {0, dict_hi, std::min<uint64_t>(R.cap, (dict_hi + 63) & ~(uint64_t)63), true, true};
+            if (R.lds_cut > dict_hi) R.pass[R.npass++] = {dict_hi, R.lds_cut, R.cap, true, false};
+        } else {
+            R.pass[R.npass++] = {0, R.lds_cut, R.cap, fast, false};
+        }
+        if (big_pass)
+            R.pass[R.npass++] = {small_lim, big_hi, std::min<uint64_t>((big_hi + 63) & ~(uint64_t)63, big_lim), false,
+                                 false};
+    }
+    // values above hbm_cut: the large-value path (pmc_deflate_large.hip), except on the V1 A/B path
+    R.lv = !force_v1 && max_len > R.hbm_cut;
+    // The HBM kernel takes values by length only on the V1 path.  Otherwise it runs gated, as the retry
+    // pass of the values this call's other paths declined (a lane-order guard fired, a large-pass value
+    // of several blocks, a large value whose segments did not stitch): it visits the call's retry list
+    // (DeflateArgs::rlist) and returns at once when the list is empty.  The latency path launches no
+    // retry pass: host_batch reads the verdicts and redoes a declined call through the pipeline.
+    R.gated = !(force_v1 && max_len > R.hbm_cut);
+    if (!R.gated || !in.latency) {
+        // as many waves as the kernel's 196 VGPRs let a CU hold (2 per SIMD) within a scratch budget
+        // (32 GiB for the V1 path's length-routed values; 8 GiB for retries, whose waves exit at once
+        // when there are none): at 2 waves per CU (round 1-2) the latency-bound walk left 64 KiB values
+        // at 0.52 GiB/s, and a 64-wave retry pass left periodic 1 MiB values and multi-block 24 KB
+        // values 32x short of that
+        // A batch of single-block values (max_len <= kSmallMax) can have retries only from a lane-order
+        // guard, which never fired on gfx950 (and a context whose create-time probe sees the order broken
+        // sends every batch to the per-lane-counter kernels instead): 64 waves, and 64 waves' scratch,
+        // cover that.  Only batches with longer values (multi-block large-pass values, large values whose
+        // segments did not stitch) size the pass for throughput (the scratch a gated pass
+        // allocates stays with the context).
+        const uint64_t cap_waves = R.gated && max_len <= in.single_block_max ? 64ull : in.cus * 8;
+        R.hbm_waves = std::max<uint64_t>(
+            1, std::min<uint64_t>(cap_waves, ((R.gated ? 8ull : 32ull) << 30) / std::max<uint64_t>(in.hbm_wb, 1)));
+    }
+    R.hbm_waves = std::min<uint64_t>(R.hbm_waves, n);
+    R.rlist = R.gated && R.hbm_waves;
+    return R;
+}
+
+} // namespace pmc

@@ -1,0 +1,101 @@
+// plan_check.cpp -- prints the plans of csrc/pmc_plan.hpp as JSON, for tests/test_host_plan.py.
+//
+//   plan_check lv <fast_seg> <budget> <table file prefix> <index>:<length> ...
+//       the rounds of these large values (fast_seg 0: exact level), one JSON object per line; round k's
+//       filled host tables are written to <prefix><k>.bin
+//   plan_check layout <pcap> <chunk>        the split pipeline's chunk arrays
+//   plan_check chunk <n> <budget> <cap>     split_chunk_of and split_value_bytes
+//   plan_check route                        one route per input line (the RouteIn fields in order, as
+//                                           integers), one JSON object per line
+#include <cinttypes>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+
+#include "../../poor-man-s-cache_amd/csrc/pmc_plan.hpp"
+
+using namespace pmc;
+
+static uint64_t u64(const char *s) { return strtoull(s, nullptr, 10); }
+
+static int lv(int argc, char **argv) {
+    if (argc < 6) return 2;
+    const uint32_t fast_seg = (uint32_t)u64(argv[2]);
+    const uint64_t budget = u64(argv[3]);
+    const std::string prefix = argv[4];
+    std::vector<std::pair<uint32_t, uint32_t>> vals;
+    for (int k = 5; k < argc; k++) {
+        const char *colon = strchr(argv[k], ':');
+        if (!colon) return 2;
+        vals.push_back({(uint32_t)u64(argv[k]), (uint32_t)u64(colon + 1)});
+    }
+    std::sort(vals.begin(), vals.end());
+    int k = 0;
+    for (size_t v0 = 0; v0 < vals.size(); k++) {
+        const LvRound r = lv_plan_round(vals.data(), vals.size(), v0, fast_seg, budget);
+        std::vector<uint64_t> image((r.tab_bytes + 7) / 8, 0xA5A5A5A5A5A5A5A5ull); // (8-byte aligned; gaps stay 0xA5)
+        r.fill((uint8_t *)image.data());
+        FILE *f = fopen((prefix + std::to_string(k) + ".bin").c_str(), "wb");
+        if (!f || fwrite(image.data(), 1, r.tab_bytes, f) != r.tab_bytes) return 3;
+        fclose(f);
+        printf("{\"v0\":%zu,\"v1\":%zu,\"nv\":%u,\"nseg\":%" PRIu64 ",\"nch\":%" PRIu64 ",\"P\":%" PRIu64 ",\"tb\":%" PRIu64
+               ",\"maxlen\":%" PRIu64,
+               r.v0, r.v1, r.nv, r.nseg, r.nch, r.P, r.tb, r.maxlen);
+        printf(",\"tab\":[%" PRIu64 ",%" PRIu64 ",%" PRIu64 ",%" PRIu64 ",%" PRIu64 ",%" PRIu64 ",%" PRIu64 "],\"tab_bytes\":%" PRIu64,
+               r.o_val, r.o_pbase, r.o_seg0, r.o_ch0, r.o_seg_val, r.o_seg_tok0, r.o_ch_val, r.tab_bytes);
+        printf(",\"scratch\":[%" PRIu64 ",%" PRIu64 ",%" PRIu64 ",%" PRIu64 ",%" PRIu64 ",%" PRIu64 ",%" PRIu64 ",%" PRIu64
+               ",%" PRIu64 "],\"scratch_bytes\":%" PRIu64 "}\n",
+               r.b_tmp, r.b_S, r.b_R, r.b_HC, r.b_hist, r.b_tok, r.b_map, r.b_seg_tok, r.b_fail, r.scratch_bytes);
+        v0 = r.v1;
+    }
+    return 0;
+}
+
+static int layout(int argc, char **argv) {
+    if (argc != 4) return 2;
+    const SplitLayout s(u64(argv[2]), u64(argv[3]));
+    printf("{\"cT\":%" PRIu64 ",\"cN\":%" PRIu64 ",\"cP\":%" PRIu64 ",\"cG\":%" PRIu64 ",\"cH\":%" PRIu64 ",\"cL\":%" PRIu64
+           ",\"cB\":%" PRIu64 ",\"cC\":%" PRIu64 ",\"cD\":%" PRIu64 ",\"cZ\":%" PRIu64 ",\"ord\":%" PRIu64 ",\"obins\":%" PRIu64
+           ",\"cQ\":%" PRIu64 ",\"bytes\":%" PRIu64 "}\n",
+           s.cT, s.cN, s.cP, s.cG, s.cH, s.cL, s.cB, s.cC, s.cD, s.cZ, s.ord, s.obins, s.cQ, s.bytes());
+    return 0;
+}
+
+static int route() {
+    char line[512];
+    while (fgets(line, sizeof line, stdin)) {
+        long long v[17];
+        int got = 0;
+        for (char *p = line, *e; got < 17; got++, p = e) {
+            v[got] = strtoll(p, &e, 10);
+            if (e == p) break;
+        }
+        if (got != 16) return 2;
+        const RouteIn in{(uint64_t)v[0], (uint64_t)v[1], (int)v[2], v[3] != 0, (uint32_t)v[4], (uint64_t)v[5],
+                         v[6] != 0, v[7] != 0, v[8] != 0, v[9] != 0, (int)v[10], (uint64_t)v[11], (uint64_t)v[12],
+                         (uint64_t)v[13], (uint64_t)v[14], (uint64_t)v[15]};
+        const Route r = plan_route(in);
+        printf("{\"kind\":\"%s\",\"passes\":[", r.kind == Route::kSplit ? "split" : r.kind == Route::kMono ? "mono" : "v1");
+        for (int k = 0; k < r.npass; k++)
+            printf("%s[%" PRIu64 ",%" PRIu64 ",%" PRIu64 ",%d,%d]", k ? "," : "", r.pass[k].lo, r.pass[k].hi, r.pass[k].pcap,
+                   (int)r.pass[k].fastp, (int)r.pass[k].dictp);
+        printf("],\"lds_cut\":%" PRIu64 ",\"cap\":%" PRIu64 ",\"dict_len\":%u,\"lv\":%d,\"fast_all\":%d,\"hbm_cut\":%" PRIu64
+               ",\"gated\":%d,\"rlist\":%d,\"hbm_waves\":%" PRIu64 "}\n",
+               r.lds_cut, r.cap, r.dict_len, (int)r.lv, (int)r.fast_all, r.hbm_cut, (int)r.gated, (int)r.rlist, r.hbm_waves);
+    }
+    return 0;
+}
+
+int main(int argc, char **argv) {
+    if (argc >= 2 && !strcmp(argv[1], "lv")) return lv(argc, argv);
+    if (argc >= 2 && !strcmp(argv[1], "layout")) return layout(argc, argv);
+    if (argc == 5 && !strcmp(argv[1], "chunk")) {
+        printf("{\"chunk\":%" PRIu64 ",\"value_bytes\":%" PRIu64 "}\n", split_chunk_of(u64(argv[2]), u64(argv[3]), u64(argv[4])),
+               split_value_bytes(u64(argv[4])));
+        return 0;
+    }
+    if (argc == 2 && !strcmp(argv[1], "route")) return route();
+    fprintf(stderr, "usage: plan_check lv|layout|chunk|route ...\n");
+    return 2;
+}
