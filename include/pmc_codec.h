@@ -44,8 +44,8 @@ typedef struct pmc_ctx pmc_ctx;
 
 /* Create a context on HIP device `device` (gfx950).  Returns PMC_OK or PMC_E_NO_DEVICE; PMC_E_ARG
  * (and a pmc_last_error text) when the environment variable PMC_LEVEL holds something else than
- * fast / 1 / fast-all / 2 / exact / 9 (see the levels below), or PMC_DICT names a file that is no dictionary (see
- * "preset dictionary"). */
+ * fast / 1 / fast-all / 2 / exact / 9 (see the levels below), PMC_INDEX something else than 1 / 0 (see "member
+ * index"), or PMC_DICT names a file that is no dictionary (see "preset dictionary"). */
 int pmc_ctx_create(int device, pmc_ctx **out);
 
 /* ---- compression level ------------------------------------------------------------------
@@ -92,6 +92,60 @@ int pmc_ctx_create(int device, pmc_ctx **out);
 #define PMC_LEVEL_FAST_ALL 2
 int pmc_ctx_set_level(pmc_ctx *ctx, int level);
 int pmc_ctx_get_level(pmc_ctx *ctx, int *level);
+
+/* ---- member index -----------------------------------------------------------------------------
+ * A DEFLATE stream cannot be entered in the middle, so one member is one decoder's work.  A context
+ * has an index switch, off by default.  With it on, a segmented fast member (PMC_LEVEL_FAST_ALL, above)
+ * is written so that every C bytes of the value decode on their own, and says where: an INDEXED MEMBER.
+ * The switch acts only where all three hold: the level is PMC_LEVEL_FAST_ALL, len > C, and
+ * K = ceil(len / C) <= 16382 (so that XLEN fits 16 bits).  C is 32768 (a multiple of the 2048-byte
+ * segment).  Every other value, at every level, with the switch on or off, gives exactly the bytes it
+ * gives without this section.
+ *
+ *    0  1f 8b 08 04   00 00 00 00   04 03         FLG = FEXTRA only, MTIME 0, XFL 4, OS 3
+ *   10  XLEN  u16 LE = 8 + 4 (K-1)
+ *   12  'P' 'I'  LEN u16 LE = 4 + 4 (K-1)         one subfield
+ *   16  version u8 = 1,  log2(C) u8,  00 00
+ *   20  (K-1) x u32 LE: byte offset, from the member's first byte, of the first block header of
+ *       chunk k, k = 1 .. K-1
+ *   20 + 4 (K-1)   chunk 0's first block header
+ *
+ * Tokens: chunk k covers value bytes [kC, min((k+1)C, len)); its tokens are the segmented fast parse of
+ * those bytes as if they were a value (tests/indexed_model.py): the history stops at the chunk's first
+ * byte, so no match reaches before its chunk.  Blocks within a chunk are as in every segmented fast
+ * member (16383 symbols, stored where smaller); a chunk's last block ends with its last token -- the
+ * last chunk's too: when the value's last token is a block's 16383rd symbol, a match or a literal, that
+ * block is the final one and no empty block follows.  After
+ * every chunk but the last comes an empty stored block -- bits 000, padding to the byte, 00 00 ff ff --
+ * so the next chunk starts on the byte the index names.  The last chunk's last block has BFINAL set;
+ * CRC-32 and ISIZE are the value's.  The member stays within pmc_gzip_bound(len): the bound's len >> 3
+ * term (4096 bytes per chunk) covers the 4 index bytes, the at most 5 separator bytes and the extra block
+ * of a chunk many times over.  A value whose parse fails the lane-order guard is redone at level 9, as
+ * above, and carries no index.
+ *
+ * It is still one valid gzip member: the reference's Decompress, zlib and gzip -d read it unchanged.
+ * This library's decompress gives each chunk to one lane of its lane decoder (csrc/pmc_inflate_chunk.hip)
+ * in every call whose max_len exceeds C.  THE INDEX IS ADVISORY: it never changes a verdict or an output
+ * byte.  A member whose index is wrong, foreign or damaged -- or whose chunks hold what the lane decoder
+ * declines (a stored block) -- decodes exactly as it would with FLG.FEXTRA skipped, through the
+ * wave-per-member kernels.  The decoder takes any 12 <= log2(C) <= 24.
+ *
+ * pmc_ctx_set_index (0 / 1; anything else, or a NULL context, gives PMC_E_ARG and touches no device)
+ * takes effect for the calls issued after it returns; stores and slabs follow their context.
+ * pmc_group_set_index sets every member context, or none.  The environment variable PMC_INDEX=1|0 sets
+ * the initial state of every context created afterwards; anything else fails pmc_ctx_create with
+ * PMC_E_ARG and a pmc_last_error text before a device is touched, as a bad PMC_LEVEL does.
+ * pmc_gzip_index_info (host only) reports the index a member carries -- the chunk size and the number
+ * of chunks -- by the decoder's own validity rules (bytes 0..3 = 1f 8b 08 04; first subfield 'P' 'I',
+ * version 1, reserved bytes 0, XLEN >= LEN + 4; 12 <= log2 C <= 24; K = LEN / 4 = ceil(ISIZE / C) >= 2;
+ * offsets strictly increasing, the first behind the header, the last below len - 8), or PMC_E_ARG when
+ * there is no valid one.  It does not check the stream.  Either output pointer may be NULL.
+ * pmc_ctx_index_counts synchronizes the device like pmc_ctx_guard_counts: counts[0] = indexed members
+ * the chunk pass completed, counts[1] = indexed members it took and then handed to the wave kernels. */
+int pmc_ctx_set_index(pmc_ctx *ctx, int on);
+int pmc_ctx_get_index(pmc_ctx *ctx, int *on);
+int pmc_gzip_index_info(const void *member, size_t len, uint32_t *chunk_bytes, uint32_t *nchunks);
+int pmc_ctx_index_counts(pmc_ctx *ctx, uint64_t counts[2]);
 
 /* ---- preset dictionary ----------------------------------------------------------------------
  * A context holds at most one dictionary of 1 .. PMC_DICT_MAX bytes (host memory at the call, copied
@@ -341,6 +395,8 @@ void pmc_group_destroy(pmc_group *g);
 int pmc_group_size(pmc_group *g);
 /* pmc_ctx_set_level on every member context (all or none). */
 int pmc_group_set_level(pmc_group *g, int level);
+/* pmc_ctx_set_index on every member context (all or none; see "member index"). */
+int pmc_group_set_index(pmc_group *g, int on);
 /* pmc_ctx_set_dictionary on every member context (all or none; see "preset dictionary"). */
 int pmc_group_set_dictionary(pmc_group *g, const void *dict, size_t len);
 /* member[i] = (key_hash[i] % num_shards) % pmc_group_size(g) */

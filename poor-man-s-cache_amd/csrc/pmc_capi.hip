@@ -188,6 +188,10 @@ struct pmc_ctx {
     // compression level of the calls issued from now on (pmc_ctx_set_level): PMC_LEVEL_EXACT, PMC_LEVEL_FAST
     // or PMC_LEVEL_FAST_ALL
     std::atomic<int> level{PMC_LEVEL_EXACT};
+    // the index switch of the calls issued from now on (pmc_ctx_set_index; include/pmc_codec.h "member index")
+    std::atomic<int> index{0};
+    DevBuf idx;                  // inflate: the chunk pass's rows (counts | fail | prefix | block sums)
+    int chunk_per_cu = 0;        // inflate: resident blocks of inflate_chunk_kernel per CU (0: not asked yet)
     // preset dictionary (pmc_ctx_set_dictionary): its bytes on the device (zero padded to a multiple of 16),
     // length and id (CRC-32; 0 = none).  Written with host_mu and both dir_mu held, read under a dir_mu.
     DevBuf dict;
@@ -360,6 +364,13 @@ static int env_level() {
     return -1;
 }
 
+// PMC_INDEX: the initial index switch of every context created from now on (unset: off).  -1: neither 0 nor 1.
+static int env_index() {
+    const char *e = getenv("PMC_INDEX");
+    if (!e) return 0;
+    return !strcmp(e, "1") ? 1 : !strcmp(e, "0") ? 0 : -1;
+}
+
 static int env_dictionary(std::vector<uint8_t> &bytes);
 static uint32_t host_crc32(const uint8_t *p, size_t n);
 static int set_dictionary_locked(pmc_ctx *ctx, const void *dict, size_t len, uint32_t id);
@@ -369,6 +380,11 @@ PMC_API int pmc_ctx_create(int device, pmc_ctx **out) {
     const int lvl = env_level();
     if (lvl < 0) {
         g_err = std::string("PMC_LEVEL=") + getenv("PMC_LEVEL") + ": expected fast, 1, fast-all, 2, exact or 9";
+        return PMC_E_ARG;
+    }
+    const int idx = env_index();
+    if (idx < 0) {
+        g_err = std::string("PMC_INDEX=") + getenv("PMC_INDEX") + ": expected 1 or 0";
         return PMC_E_ARG;
     }
     std::vector<uint8_t> env_dict; // PMC_DICT: checked before any device is touched, as PMC_LEVEL
@@ -422,6 +438,7 @@ PMC_API int pmc_ctx_create(int device, pmc_ctx **out) {
     pmc_ctx *c = new pmc_ctx;
     c->device = device;
     c->cus = prop.multiProcessorCount;
+    c->index = idx;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&c->dir_ev[0], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->dir_ev[1], hipEventDisableTiming) != hipSuccess) {
@@ -430,7 +447,8 @@ PMC_API int pmc_ctx_create(int device, pmc_ctx **out) {
     }
     // guard counters, and the lane-order self-test (lane_order_probe_kernel: 4 waves x 512 trials)
     uint32_t probe = 0;
-    if (c->guard.ensure(32) || hipMemsetAsync(c->guard.p, 0, 32, c->stream) != hipSuccess) {
+    // (bytes 32..47: the chunk pass's two u64 counters, pmc_ctx_index_counts)
+    if (c->guard.ensure(64) || hipMemsetAsync(c->guard.p, 0, 64, c->stream) != hipSuccess) {
         pmc_ctx_destroy(c);
         return PMC_E_NO_DEVICE;
     }
@@ -469,6 +487,35 @@ PMC_API int pmc_ctx_set_level(pmc_ctx *ctx, int level) {
 PMC_API int pmc_ctx_get_level(pmc_ctx *ctx, int *level) {
     if (!ctx || !level) return PMC_E_ARG;
     *level = ctx->level;
+    return PMC_OK;
+}
+
+// ---- member index (include/pmc_codec.h "member index") ---------------------------------------------------
+PMC_API int pmc_ctx_set_index(pmc_ctx *ctx, int on) {
+    if (!ctx || (on != 0 && on != 1)) return PMC_E_ARG;
+    ctx->index = on;
+    return PMC_OK;
+}
+
+PMC_API int pmc_ctx_get_index(pmc_ctx *ctx, int *on) {
+    if (!ctx || !on) return PMC_E_ARG;
+    *on = ctx->index;
+    return PMC_OK;
+}
+
+PMC_API int pmc_gzip_index_info(const void *member, size_t len, uint32_t *chunk_bytes, uint32_t *nchunks) {
+    uint32_t lg = 0, K = 0, isz = 0, hdr = 0;
+    if (!member || !idx_parse((const uint8_t *)member, len, &lg, &K, &isz, &hdr)) return PMC_E_ARG;
+    if (chunk_bytes) *chunk_bytes = 1u << lg;
+    if (nchunks) *nchunks = K;
+    return PMC_OK;
+}
+
+PMC_API int pmc_ctx_index_counts(pmc_ctx *ctx, uint64_t counts[2]) {
+    if (!ctx || !counts) return PMC_E_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(counts, (uint8_t *)ctx->guard.p + 32, 16, hipMemcpyDeviceToHost));
     return PMC_OK;
 }
 
@@ -619,6 +666,7 @@ PMC_API void pmc_ctx_destroy(pmc_ctx *c) {
     c->crcx.release();
     c->recs.release();
     c->bigl.release();
+    c->idx.release();
     c->dict.release();
     c->guard.release();
     c->rlist.release();
@@ -748,6 +796,8 @@ static int large_values(pmc_ctx *ctx, const DeflateArgs &a, uint64_t lo, uint64_
     for (uint32_t k = 0; k < cnt; k++) vals[k] = {list[2 * k], list[2 * k + 1]};
     std::sort(vals.begin(), vals.end());
     const uint64_t budget = 24ull << 30;
+    // (the index switch acts on the segmented fast members only; read once per call)
+    const uint32_t idx_chunk = fast && ctx->index ? kIdxChunk : 0u;
     const uint64_t fwb = fast ? lv_fast_wave_bytes() : 0;
     const Launch Lp = fast ? plan_lds(ctx, (const void *)lv_fast_parse_kernel, fwb, 1ull << 40, 0) : Launch{};
     for (size_t v0 = 0; v0 < vals.size();) {
@@ -788,6 +838,7 @@ static int large_values(pmc_ctx *ctx, const DeflateArgs &a, uint64_t lo, uint64_
         // gzip XFL: the reference's header for an exact member; zlib's "fastest algorithm" for a fast one, as
         // the small fast members
         L.xfl = fast ? 4 : 2;
+        L.idx_chunk = idx_chunk;
         if (fast) {
             HIP_TRY(hipMemsetAsync(L.fail, 0, 4ull * R.nv, st));
             DeflateArgs p = a;
@@ -1077,6 +1128,58 @@ static uint64_t inflate_lds_limit_out(uint64_t max_len) {
     return (c + 63) & ~(uint64_t)63;
 }
 
+// ---- indexed members (pmc_inflate_chunk.hip; include/pmc_codec.h "member index") --------------------------
+namespace {
+int scan_u32(const uint32_t *v, const int32_t *rc, uint32_t n, uint64_t *out, uint64_t *bsum, hipStream_t st);
+constexpr uint32_t kIdxScanBlock = 1024; // (= kScanBlock: scan_u32's block sums, one per so many members)
+} // namespace
+
+// The chunk pass up to the CRC check: which members carry a valid index (all: of every member, the wave-only
+// route; else of those the lane passes left kInflateRetry), a prefix sum of their chunk counts, one lane per
+// chunk, then rc / dst_len / crc_expect of the members whose chunks all decoded.  Enqueue only, no readback;
+// the rows in ctx->idx are O(n).  The caller runs inflate_verify_kernel, then chunk_pass_count.
+static int chunk_pass_decode(pmc_ctx *ctx, const InflateArgs &a, ChunkArgs &X, bool all, hipStream_t st) {
+    const uint64_t n = a.n, nb = (n + kIdxScanBlock - 1) / kIdxScanBlock;
+    const uint64_t o_fail = 4 * n, o_pre = (8 * n + 7) & ~(uint64_t)7, o_bsum = o_pre + 8 * n;
+    int r = ctx->idx.ensure(o_bsum + 8 * (nb + 1));
+    if (r) return r;
+    uint8_t *p = (uint8_t *)ctx->idx.p;
+    uint64_t *bsum = (uint64_t *)(p + o_bsum);
+    X.cnt = (uint32_t *)p;
+    X.fail = (uint32_t *)(p + o_fail);
+    X.pre = (uint64_t *)(p + o_pre);
+    X.total = bsum + nb;
+    X.counts = (uint64_t *)((uint8_t *)ctx->guard.p + 32);
+    X.all = all ? 1 : 0;
+    const unsigned mb = (unsigned)std::min<uint64_t>((n + 255) / 256, (uint64_t)ctx->cus * 8);
+    klaunch(ctx, PMC_K_ORDER, st, [&] {
+        hipLaunchKernelGGL(inflate_chunk_scan_kernel, dim3(mb), dim3(256), 0, st, a, X);
+        r = scan_u32(X.cnt, nullptr, (uint32_t)n, (uint64_t *)(p + o_pre), bsum, st);
+    });
+    if (r) return r; // (scan_u32 has named the launch that failed)
+    // (the item count stays on the device: a grid of the resident waves strides over the items, and returns
+    // at once when there are none)
+    // (asked once per context, under its decompress lock: a context is one device)
+    if (!ctx->chunk_per_cu) ctx->chunk_per_cu = occupancy_blocks((const void *)inflate_chunk_kernel, 64, kChunkLdsBytes);
+    const unsigned cb =
+        (unsigned)std::min<uint64_t>((uint64_t)ctx->cus * ctx->chunk_per_cu, (n * kIdxMaxChunks + 63) / 64);
+    klaunch(ctx, PMC_K_INFLATE_LANE, st, [&] {
+        hipLaunchKernelGGL(inflate_chunk_kernel, dim3(cb), dim3(64), kChunkLdsBytes, st, a, X);
+        hipLaunchKernelGGL(inflate_chunk_finish_kernel, dim3(mb), dim3(256), 0, st, a, X);
+    });
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_err("inflate_chunk_kernel", e);
+        return PMC_E_NO_DEVICE;
+    }
+    return PMC_OK;
+}
+static void chunk_pass_count(pmc_ctx *ctx, const InflateArgs &a, const ChunkArgs &X, hipStream_t st) {
+    const unsigned mb = (unsigned)std::min<uint64_t>((a.n + 255) / 256, (uint64_t)ctx->cus * 8);
+    klaunch(ctx, PMC_K_INFLATE_LANE, st,
+            [&] { hipLaunchKernelGGL(inflate_chunk_count_kernel, dim3(mb), dim3(256), 0, st, a, X); });
+}
+
 static int decompress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t *src_off,
                                  const uint32_t *src_len, uint32_t n, uint8_t *dst, const uint64_t *dst_off,
                                  const uint32_t *dst_cap, uint32_t *dst_len, int32_t *rc, uint32_t max_len,
@@ -1098,6 +1201,33 @@ static int decompress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_
     static const bool wave_only = getenv("PMC_INFLATE_WAVE") && atoi(getenv("PMC_INFLATE_WAVE"));
     // (round 4 measured routing batches of <= 2048 members to the wave kernels instead: 256 x 4 KiB took
     // 12.5 ms there against 3.2 ms for 4096 members through the lane / record paths -- not done)
+    // The chunk pass over indexed members runs in every call that may hold one (a member of more than one
+    // chunk decodes to more than kIdxChunk bytes), on either route; with PMC_INFLATE_WAVE=1 it is off, like
+    // the other fast paths.  A call with max_len <= kIdxChunk launches nothing for it.
+    const bool chunk_pass = !wave_only && max_len > kIdxChunk;
+    ChunkArgs X{};
+    auto verify = [&] { // CRC-32 of every member the lane decoders finished (rc 0)
+        // (members per wave as for the record kernel: a small batch takes one wave per member)
+        uint32_t VG = 1;
+        while (VG < 64 && ((uint64_t)n + VG - 1) / VG > (uint64_t)ctx->cus * 32) VG *= 2;
+        a.verify_group = VG;
+        const unsigned vb = (unsigned)std::min<uint64_t>(((uint64_t)n + 8ull * VG - 1) / (8ull * VG), (uint64_t)ctx->cus * 4);
+        klaunch(ctx, PMC_K_INFLATE_VERIFY, st,
+                [&] { hipLaunchKernelGGL(inflate_verify_kernel, dim3(vb), dim3(512), 0, st, a); });
+    };
+    if (chunk_pass && latency) {
+        // the wave-only route (a small batch, or at most 4 members per CU -- where 1000 x 1 MiB lands): the
+        // chunk pass takes the indexed members, marks every other one kInflateRetry, and the wave kernels
+        // below run retry_only (uncounted: pmc_ctx_guard_counts counts[4] is the pipeline route's)
+        int r = ctx->crcx.ensure((uint64_t)n * 4);
+        if (r) return r;
+        a.crc_expect = (uint32_t *)ctx->crcx.p;
+        r = chunk_pass_decode(ctx, a, X, true, st);
+        if (r) return r;
+        verify();
+        chunk_pass_count(ctx, a, X, st);
+        a.retry_only = 1;
+    }
     if (!wave_only && !latency) {
         int r = ctx->crcx.ensure((uint64_t)n * 4);
         if (r) return r;
@@ -1180,13 +1310,13 @@ static int decompress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_
         a.big_only = 0;
         a.big_list = nullptr;
         a.big_count = nullptr;
-        // (members per wave as for the record kernel: a small batch takes one wave per member)
-        uint32_t VG = 1;
-        while (VG < 64 && ((uint64_t)n + VG - 1) / VG > (uint64_t)ctx->cus * 32) VG *= 2;
-        a.verify_group = VG;
-        const unsigned vb = (unsigned)std::min<uint64_t>(((uint64_t)n + 8ull * VG - 1) / (8ull * VG), (uint64_t)ctx->cus * 4);
-        klaunch(ctx, PMC_K_INFLATE_VERIFY, st,
-                [&] { hipLaunchKernelGGL(inflate_verify_kernel, dim3(vb), dim3(512), 0, st, a); });
+        // indexed members (FLG = FEXTRA: the lane passes declined them), one lane per chunk
+        if (chunk_pass) {
+            r = chunk_pass_decode(ctx, a, X, false, st);
+            if (r) return r;
+        }
+        verify();
+        if (chunk_pass) chunk_pass_count(ctx, a, X, st);
         a.retry_only = 1;
         a.retried = (uint32_t *)ctx->guard.p + 4; // (pmc_ctx_guard_counts counts[4])
         a.order = nullptr;
@@ -1641,6 +1771,7 @@ __global__ void rebase_kernel(uint64_t *soff, uint64_t *doff, uint32_t n, uint64
 // Exclusive prefix sum of v[i] (0 where rc[i] != 0, if rc is given) into out[]; kScanBlock values per
 // block, block totals to bsum[] (scan_blocks_kernel turns them into block bases, bsum[nb] = total).
 constexpr uint32_t kScanBlock = 1024;
+static_assert(kScanBlock == kIdxScanBlock, "the chunk pass sizes scan_u32's block sums");
 __global__ __launch_bounds__(kScanBlock) void scan_local_kernel(const uint32_t *v, const int32_t *rc, uint32_t n,
                                                                  uint64_t *out, uint64_t *bsum) {
     __shared__ uint64_t s[kScanBlock];

@@ -397,12 +397,21 @@ struct DeflateWave {
         for (uint64_t k = l; k < out_words; k += 64) outw[k] = 0;
         for (int k = l; k < 320; k += 64) hist[k] = 0;
         sync();
+        // an indexed value (include/pmc_codec.h "member index"): FLG = FEXTRA, and the 'P' 'I' subfield whose
+        // offsets are filled in as the chunks are reached
+        const IdxPlan ix = idx_plan(len, L.idx_chunk);
         if (l < 10) {
             const uint8_t hdr[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 2, 3};
-            outb[l] = l == 8 ? (uint8_t)L.xfl : hdr[l];
+            outb[l] = l == 8 ? (uint8_t)L.xfl : l == 3 && ix.indexed ? (uint8_t)4 : hdr[l];
+        } else if (l < 20 && ix.indexed) {
+            // bytes 10..17: XLEN | 'P' 'I' | LEN | version 1 | log2 C, then 00 00 (shifted out of one word: a local
+            // array indexed by the lane would live in scratch memory)
+            const uint64_t xlen = ix.hdr - 12, sl = xlen - 4, lg = 31 - __builtin_clz(L.idx_chunk);
+            const uint64_t ext = xlen | (uint64_t)'P' << 16 | (uint64_t)'I' << 24 | sl << 32 | 1ull << 48 | lg << 56;
+            outb[l] = l < 18 ? (uint8_t)(ext >> (8 * (l - 10))) : (uint8_t)0;
         }
         sync();
-        uint64_t bitpos = 80, pos = 0, block_start = 0, last_start = 0;
+        uint64_t bitpos = (uint64_t)ix.hdr * 8, pos = 0, block_start = 0, last_start = 0;
         uint32_t ntok = 0;
         auto flush = [&](bool last) {
             // freqs -> the trees (init_block: END_BLOCK counted once)
@@ -427,7 +436,19 @@ struct DeflateWave {
             sync();
         };
         const uint32_t g0 = L.lv_seg0[ov], g1 = L.lv_seg0[ov + 1];
+        const uint32_t cseg = ix.indexed ? L.idx_chunk / kIdxSeg : 0u; // segments per chunk
         for (uint32_t g = g0; g < g1; g++) {
+            if (ix.indexed && g != g0 && (g - g0) % cseg == 0) {
+                // a chunk ends here: its last block, then the empty stored block (bits 000, already zero in
+                // the image, padding to the byte, 00 00 ff ff); the next chunk's first block header starts
+                // on the byte the index names
+                if (ntok) flush(false);
+                const uint64_t o = (bitpos + 3 + 7) >> 3;
+                if (l < 4) outb[o + l] = l < 2 ? (uint8_t)0 : (uint8_t)0xff;
+                if (l == 4) outw[kIdxHdrFixed / 4 + (g - g0) / cseg - 1] = (uint32_t)(o + 4);
+                bitpos = (o + 4) * 8;
+                sync();
+            }
             const uint32_t *tk = L.tok + L.seg_tok0[g];
             uint32_t t = L.seg_tok[(uint64_t)g * 4 + 1];
             const uint32_t te = L.seg_tok[(uint64_t)g * 4 + 2];
@@ -454,7 +475,9 @@ struct DeflateWave {
                 // zlib's deflate_slow tallies a value's last literal after its loop, where a full symbol buffer
                 // does not flush (deflate.c: _tr_tally_lit, then FLUSH_BLOCK(s, 1)): when that literal is the
                 // block's 16383rd symbol it ends the final block, not a block of its own before an empty one
-                const bool tail_lit = pos == len && readlane(dist, (int)take - 1) == 0u;
+                // (an indexed member: every chunk's last block ends with its last token, so the value's last token
+                // ends the final block whatever it is -- no empty final block after a 16383rd symbol)
+                const bool tail_lit = pos == len && (ix.indexed || readlane(dist, (int)take - 1) == 0u);
                 if (ntok == kSymsPerBlock && !tail_lit) flush(false);
             }
         }

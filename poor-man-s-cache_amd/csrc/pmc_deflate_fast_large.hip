@@ -24,6 +24,7 @@ namespace pmc {
 constexpr uint32_t kFlSeg = 2048, kFlHist = 2048;
 constexpr uint32_t kFlCap = (kFlSeg + kFlHist + 63) & ~63u; // the LDS layout's capacity
 static_assert(kFlSeg + kFlHist <= kSmallMax && kFlCap <= 16384, "fast large-value segment span");
+static_assert(kIdxSeg == kFlSeg && kIdxChunk % kFlSeg == 0, "an index chunk is whole segments");
 
 uint64_t lv_fast_wave_bytes() { return fast_layout(kFlCap).total; }
 
@@ -49,7 +50,9 @@ __global__ void __launch_bounds__(256) lv_fast_parse_kernel(DeflateArgs a, Large
         const uint64_t s0 = (sg - L.lv_seg0[ov]) * (uint64_t)kFlSeg;
         uint32_t ntok = 0;
         if (s0 < len) { // (the host cut the value into ceil(len / kFlSeg) segments)
-            const uint32_t h = s0 < kFlHist ? (uint32_t)s0 : kFlHist;
+            // (an indexed value's history stops at its chunk's first byte: chunks decode independently)
+            const uint64_t hs = idx_plan(len, L.idx_chunk).indexed ? s0 & (uint64_t)(L.idx_chunk - 1) : s0;
+            const uint32_t h = hs < kFlHist ? (uint32_t)hs : kFlHist;
             const uint32_t seglen = len - s0 < kFlSeg ? (uint32_t)(len - s0) : kFlSeg;
             const uint32_t T = h + seglen; // staged bytes: <= kFlHist + kFlSeg <= kFlCap
             w.tok = (PMC_GLB uint32_t *)(L.tok + L.seg_tok0[sg]);
@@ -63,7 +66,7 @@ __global__ void __launch_bounds__(256) lv_fast_parse_kernel(DeflateArgs a, Large
                 ntok = F.pk == 6   ? fw.parse<6, true>(npos, T, h)
                        : F.pk == 4 ? fw.parse<4, true>(npos, T, h)
                                    : fw.parse<0, true>(npos, T, h);
-            } else { // (a first segment of one or two bytes: never with the host's routing)
+            } else { // (one or two bytes behind nothing: an indexed value's last chunk)
                 if ((uint32_t)l < T) w.tok[l] = w.b[l];
                 ntok = T;
             }

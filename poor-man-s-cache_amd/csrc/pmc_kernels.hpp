@@ -118,6 +118,9 @@ struct LargeArgs {
     uint32_t *seg_tok;        // [nseg][4]: tokens parsed, stitched begin, stitched end, (unused)
     int32_t *fail;            // [nv] no convergence at some boundary: the HBM kernel redoes the value
     uint32_t xfl;             // gzip header byte 8 the emit writes: 2 for an exact member, 4 for a segmented fast one
+    // the fast parse and its emit: chunk bytes of the member index (idx_plan, pmc_plan.hpp), 0 = the switch is
+    // off (include/pmc_codec.h "member index")
+    uint32_t idx_chunk;
 };
 __global__ void lv_select_kernel(const uint32_t *src_len, uint64_t n, uint64_t lo, uint64_t hi, uint32_t *out);
 __global__ void lv_sort_hist_kernel(LargeArgs a, int pass);
@@ -265,6 +268,20 @@ template <uint32_t OUT>
 __global__ void inflate_rec_kernel(InflateArgs a);
 uint32_t rec_lds_bytes(uint32_t out); // dynamic LDS of inflate_rec_kernel<out>
 __global__ void inflate_verify_kernel(InflateArgs a);
+// the chunk pass over indexed members (pmc_inflate_chunk.hip; include/pmc_codec.h "member index"): scratch
+// of O(n), one row per member
+struct ChunkArgs {
+    uint32_t *cnt;         // [n] chunks of the member, 0 = the pass does not take it
+    const uint64_t *pre;   // [n] exclusive prefix sum of cnt: the member's first item
+    const uint64_t *total; // the number of items (chunks of taken members)
+    uint32_t *fail;        // [n] some chunk of the member did not decode as its index says
+    uint64_t *counts;      // the context's counters (pmc_ctx_index_counts)
+    int32_t all;           // scan: look at every member (the wave-only route), not only at kInflateRetry ones
+};
+__global__ void inflate_chunk_scan_kernel(InflateArgs a, ChunkArgs X);
+__global__ void inflate_chunk_kernel(InflateArgs a, ChunkArgs X);
+__global__ void inflate_chunk_finish_kernel(InflateArgs a, ChunkArgs X);
+__global__ void inflate_chunk_count_kernel(InflateArgs a, ChunkArgs X);
 __global__ void arg_check_kernel(const uint32_t *src_len, uint64_t n, uint64_t max_len, int32_t *rc,
                                  uint32_t *dst_len);
 __global__ void lane_order_probe_kernel(uint32_t trials, uint32_t *violations);

@@ -137,6 +137,72 @@ inline LvRound lv_plan_round(const std::pair<uint32_t, uint32_t> *vals, size_t n
     return r;
 }
 
+// ---- member index (include/pmc_codec.h "member index") ---------------------------------------------------
+#if defined(__HIPCC__)
+#define PMC_HD __host__ __device__
+#else
+#define PMC_HD
+#endif
+// chunk bytes of the members this library writes (a power of two, a multiple of the fast parse's segment;
+// the decoder reads every 2^12 .. 2^24 from the header)
+#ifndef PMC_IDX_CHUNK
+#define PMC_IDX_CHUNK 32768
+#endif
+constexpr uint32_t kIdxChunk = PMC_IDX_CHUNK;
+constexpr uint32_t kIdxMaxChunks = 16382;          // XLEN = 8 + 4 (K - 1) fits 16 bits
+constexpr uint32_t kIdxHdrFixed = 20;              // header bytes before the offsets
+constexpr uint32_t kIdxSeg = 2048;                 // the fast parse's segment (kFlSeg): a chunk is whole segments
+constexpr uint32_t kIdxLog2Min = 12, kIdxLog2Max = 24;
+static_assert((kIdxChunk & (kIdxChunk - 1)) == 0 && kIdxChunk >= (1u << kIdxLog2Min) && kIdxChunk <= (1u << kIdxLog2Max),
+              "index chunk size");
+
+// What the index switch makes of a fast-all value of `len` bytes with chunks of C bytes (C 0: switch off):
+// K chunks behind a header of hdr bytes when indexed, else the plain member (K 1, hdr 10).
+struct IdxPlan {
+    bool indexed;
+    uint32_t K, hdr;
+};
+PMC_HD inline IdxPlan idx_plan(uint64_t len, uint32_t C) {
+    IdxPlan p{false, 1, 10};
+    if (C == 0 || len <= C) return p;
+    const uint64_t K = (len + C - 1) / C;
+    if (K > kIdxMaxChunks) return p;
+    p.indexed = true;
+    p.K = (uint32_t)K;
+    p.hdr = kIdxHdrFixed + 4 * (p.K - 1);
+    return p;
+}
+
+// The index a member carries, by the rules of inflate_chunk_scan_kernel (all but the capacity one): bytes
+// 0..3 = 1f 8b 08 04, the first FEXTRA subfield 'P' 'I' of version 1 with XLEN >= LEN + 4, LEN = 4 + 4 (K - 1),
+// reserved bytes 0, 12 <= log2 C <= 24, K = ceil(ISIZE / C) >= 2, offsets strictly increasing from behind
+// the header to below len - 8.  *hdr: the first byte behind the header.  (P: any pointer to bytes)
+template <class P>
+PMC_HD inline bool idx_parse(P m, uint64_t len, uint32_t *log2c, uint32_t *K, uint32_t *isize, uint32_t *hdr) {
+    if (len < kIdxHdrFixed + 4 + 8 + 1) return false;
+    if (m[0] != 0x1f || m[1] != 0x8b || m[2] != 8 || m[3] != 4) return false;
+    const uint32_t xlen = (uint32_t)m[10] | (uint32_t)m[11] << 8, sl = (uint32_t)m[14] | (uint32_t)m[15] << 8;
+    if (m[12] != 'P' || m[13] != 'I' || sl < 8 || (sl & 3) != 0 || xlen < sl + 4) return false;
+    if (m[16] != 1 || m[18] != 0 || m[19] != 0) return false;
+    const uint32_t lg = m[17], k = sl / 4, h = 12 + xlen;
+    if (lg < kIdxLog2Min || lg > kIdxLog2Max || (uint64_t)h + 8 >= len) return false;
+    const uint32_t isz = (uint32_t)m[len - 4] | (uint32_t)m[len - 3] << 8 | (uint32_t)m[len - 2] << 16 |
+                         (uint32_t)m[len - 1] << 24;
+    if (k < 2 || (uint32_t)(((uint64_t)isz + (1u << lg) - 1) >> lg) != k) return false;
+    uint64_t prev = h;
+    for (uint32_t j = 0; j + 1 < k; j++) {
+        const uint32_t at = kIdxHdrFixed + 4 * j;
+        const uint64_t o = (uint32_t)m[at] | (uint32_t)m[at + 1] << 8 | (uint32_t)m[at + 2] << 16 | (uint32_t)m[at + 3] << 24;
+        if (o <= prev || o + 8 >= len) return false;
+        prev = o;
+    }
+    *log2c = lg;
+    *K = k;
+    *isize = isz;
+    *hdr = h;
+    return true;
+}
+
 // ---- split pipeline chunk arrays (DeflateArgs cT .. cQ; pmc_deflate_split.hip) -------------------------
 constexpr uint32_t kSplitRows = 336;  // 286 lit/len + 30 dist + 19 bit-length (+1)
 constexpr uint32_t kMergeRows = 572;  // 2 heap entries per merge, <= 285 merges

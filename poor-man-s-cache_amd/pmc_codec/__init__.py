@@ -98,6 +98,11 @@ SIGNATURES = {
     "pmc_ctx_set_dictionary": (_c.c_int, [_p, _c.c_char_p, _c.c_size_t]),
     "pmc_ctx_get_dictionary_id": (_c.c_int, [_p, _c.POINTER(_u32)]),
     "pmc_group_set_dictionary": (_c.c_int, [_p, _c.c_char_p, _c.c_size_t]),
+    "pmc_ctx_set_index": (_c.c_int, [_p, _c.c_int]),
+    "pmc_ctx_get_index": (_c.c_int, [_p, _c.POINTER(_c.c_int)]),
+    "pmc_group_set_index": (_c.c_int, [_p, _c.c_int]),
+    "pmc_gzip_index_info": (_c.c_int, [_c.c_char_p, _c.c_size_t, _c.POINTER(_u32), _c.POINTER(_u32)]),
+    "pmc_ctx_index_counts": (_c.c_int, [_p, _c.POINTER(_u64)]),
 }
 
 # compression levels (include/pmc_codec.h PMC_LEVEL_*)
@@ -169,6 +174,16 @@ def gzip_bounds(lengths):
     return (n + (n >> np.uint64(3)) + np.uint64(6) * (n // np.uint64(16383) + np.uint64(1)) + np.uint64(32)).astype(np.uint32)
 
 
+def index_info(member: bytes):
+    """(chunk_bytes, nchunks) of the index a gzip member carries, or None when it carries no valid one
+    (include/pmc_codec.h pmc_gzip_index_info).  Host only; the stream is not checked."""
+    member = bytes(member)
+    c, k = _u32(0), _u32(0)
+    if lib().pmc_gzip_index_info(member, len(member), ctypes.byref(c), ctypes.byref(k)) != 0:
+        return None
+    return c.value, k.value
+
+
 def decompress_capacity(member: bytes) -> int:
     """Output capacity for one gzip member: its ISIZE trailer, clamped to DEFLATE's
     1032:1 maximum expansion (a larger ISIZE cannot belong to a valid member)."""
@@ -205,6 +220,32 @@ class Context:
         rc = lib().pmc_ctx_set_level(self.handle, int(value))
         if rc != 0:
             raise ValueError(f"pmc_ctx_set_level({value}) = {rc}")
+
+    @property
+    def index(self) -> bool:
+        """The index switch (include/pmc_codec.h "member index"): with it on, LEVEL_FAST_ALL values above 32 KiB
+        become indexed members, whose chunks this library decodes in parallel.  Setting it takes effect for
+        the calls issued afterwards."""
+        v = _c.c_int(0)
+        rc = lib().pmc_ctx_get_index(self.handle, ctypes.byref(v))
+        if rc != 0:
+            raise CodecUnavailable(f"pmc_ctx_get_index failed ({rc})")
+        return bool(v.value)
+
+    @index.setter
+    def index(self, on):
+        rc = lib().pmc_ctx_set_index(self.handle, int(on))
+        if rc != 0:
+            raise ValueError(f"pmc_ctx_set_index({on}) = {rc}")
+
+    def index_counts(self):
+        """{completed, handed_over}: indexed members the chunk pass decoded / took and then left to the wave
+        kernels (include/pmc_codec.h pmc_ctx_index_counts)."""
+        c = (_u64 * 2)()
+        rc = lib().pmc_ctx_index_counts(self.handle, c)
+        if rc != 0:
+            raise CodecUnavailable(f"pmc_ctx_index_counts failed ({rc}): {last_error()}")
+        return {"completed": c[0], "handed_over": c[1]}
 
     def set_dictionary(self, dictionary):
         """Preset dictionary of 1 .. DICT_MAX bytes (None or b"" clears it): fast-level values of
