@@ -191,7 +191,9 @@ struct pmc_ctx {
     // the index switch of the calls issued from now on (pmc_ctx_set_index; include/pmc_codec.h "member index")
     std::atomic<int> index{0};
     DevBuf idx;                  // inflate: the chunk pass's rows (counts | fail | prefix | block sums)
-    int chunk_per_cu = 0;        // inflate: resident blocks of inflate_chunk_kernel per CU (0: not asked yet)
+    // inflate: resident blocks per CU of inflate_chunk_kernel and of the record kernel's 4 KiB [0] and 1 KiB [1]
+    // instances (0: not asked yet; asked under the decompress lock)
+    int chunk_per_cu = 0, rec_per_cu[2] = {0, 0};
     // preset dictionary (pmc_ctx_set_dictionary): its bytes on the device (zero padded to a multiple of 16),
     // length and id (CRC-32; 0 = none).  Written with host_mu and both dir_mu held, read under a dir_mu.
     DevBuf dict;
@@ -279,9 +281,10 @@ struct Launch {
     size_t lds;     // dynamic LDS per block
 };
 
-int occupancy_blocks(const void *kernel, int threads, size_t lds) {
+// (fallback: the answer when the runtime gives none)
+int occupancy_blocks(const void *kernel, int threads, size_t lds, int fallback = 1) {
     int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, threads, lds) != hipSuccess || nb < 1) nb = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, threads, lds) != hipSuccess || nb < 1) nb = fallback;
     return nb;
 }
 
@@ -734,18 +737,9 @@ static uint64_t latency_batch() {
     static const uint64_t v = getenv("PMC_LATENCY_BATCH") ? (uint64_t)atoll(getenv("PMC_LATENCY_BATCH")) : kLatencyBatch;
     return v;
 }
-static uint64_t inflate_lds_out_limit();
-// the decompress side's length limit: the wave-per-member inflate kernel's LDS image (48 KiB)
-static uint64_t latency_max_out() {
-    return latency_max_len() ? std::max(latency_max_len(), inflate_lds_out_limit()) : 0;
-}
-// the decompress side's batch limit: 4x the compress side's, with at most 4x the output in all (4,096 x
-// 4 KiB members: 0.81 ms device-resident through the wave kernel against 1.69 ms through the pipeline;
-// compress at 4,096 x 4 KiB is faster through the pipeline, 2.86 against 3.33 ms -- round 5, same box)
-static bool latency_decompress(uint64_t n, uint64_t max_out, uint64_t out_bytes) {
-    const uint64_t lb = 4 * latency_batch(), lm = latency_max_len();
-    return n <= lb && max_out <= latency_max_out() && (max_out <= lm || out_bytes <= lb * lm);
-}
+// the largest output image of the wave-per-member inflate kernel's LDS variant: the decompress side's length
+// limit on the latency path (inflate_latency, pmc_plan.hpp, states the route)
+constexpr uint64_t kInflateLdsOut = 48 * 1024;
 
 // ---- kernel instances ----------------------------------------------------------------------------------
 // Each is chosen once, as a typed pointer: the same pointer feeds the occupancy plan and the launch.
@@ -1121,51 +1115,137 @@ static int compress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t 
     return PMC_OK;
 }
 
-static uint64_t inflate_lds_out_limit() { return 48 * 1024; }
-// the output image decompress_batch_body's LDS wave kernel gets for a call with this max_len
-static uint64_t inflate_lds_limit_out(uint64_t max_len) {
-    const uint64_t c = std::min<uint64_t>(inflate_lds_out_limit(), std::max<uint64_t>(max_len, 1));
-    return (c + 63) & ~(uint64_t)63;
-}
-
-// ---- indexed members (pmc_inflate_chunk.hip; include/pmc_codec.h "member index") --------------------------
+// ---- a decompress call: plan_inflate (pmc_plan.hpp: which stages run, their grids and scratch, and why) ->
+// order, record kernel, lane passes, chunk pass, CRC check, wave kernels --------------------------------------
 namespace {
 int scan_u32(const uint32_t *v, const int32_t *rc, uint32_t n, uint64_t *out, uint64_t *bsum, hipStream_t st);
 constexpr uint32_t kIdxScanBlock = 1024; // (= kScanBlock: scan_u32's block sums, one per so many members)
 } // namespace
 
-// The chunk pass up to the CRC check: which members carry a valid index (all: of every member, the wave-only
-// route; else of those the lane passes left kInflateRetry), a prefix sum of their chunk counts, one lane per
-// chunk, then rc / dst_len / crc_expect of the members whose chunks all decoded.  Enqueue only, no readback;
-// the rows in ctx->idx are O(n).  The caller runs inflate_verify_kernel, then chunk_pass_count.
-static int chunk_pass_decode(pmc_ctx *ctx, const InflateArgs &a, ChunkArgs &X, bool all, hipStream_t st) {
-    const uint64_t n = a.n, nb = (n + kIdxScanBlock - 1) / kIdxScanBlock;
-    const uint64_t o_fail = 4 * n, o_pre = (8 * n + 7) & ~(uint64_t)7, o_bsum = o_pre + 8 * n;
-    int r = ctx->idx.ensure(o_bsum + 8 * (nb + 1));
-    if (r) return r;
-    uint8_t *p = (uint8_t *)ctx->idx.p;
-    uint64_t *bsum = (uint64_t *)(p + o_bsum);
-    X.cnt = (uint32_t *)p;
-    X.fail = (uint32_t *)(p + o_fail);
-    X.pre = (uint64_t *)(p + o_pre);
-    X.total = bsum + nb;
-    X.counts = (uint64_t *)((uint8_t *)ctx->guard.p + 32);
-    X.all = all ? 1 : 0;
-    const unsigned mb = (unsigned)std::min<uint64_t>((n + 255) / 256, (uint64_t)ctx->cus * 8);
+// the A/B switches of the decompress path, read once per process
+struct InflateEnv {
+    bool wave_only, no_order, no_rec; // PMC_INFLATE_WAVE=1, PMC_INFLATE_ORDER=0, PMC_INFLATE_REC=0
+};
+static const InflateEnv &inflate_env() {
+    auto value = [](const char *name, int unset) { return getenv(name) ? atoi(getenv(name)) : unset; };
+    static const InflateEnv e{value("PMC_INFLATE_WAVE", 0) != 0, value("PMC_INFLATE_ORDER", 1) == 0,
+                              value("PMC_INFLATE_REC", 1) == 0};
+    return e;
+}
+
+static InflateIn inflate_in(pmc_ctx *ctx, uint32_t n, uint32_t max_len, bool latency, bool need_hbm) {
+    // (asked once per context, under its decompress lock: a context is one device)
+    if (!ctx->chunk_per_cu) {
+        for (int k = 0; k < 2; k++) {
+            const uint32_t rlds = rec_lds_bytes(k ? 1024 : kRecOutMax);
+            ctx->rec_per_cu[k] = occupancy_blocks((const void *)rec_kernel(k != 0), 64, rlds, (int)(kLdsPerCu / rlds));
+        }
+        ctx->chunk_per_cu = occupancy_blocks((const void *)inflate_chunk_kernel, 64, kChunkLdsBytes);
+    }
+    const InflateEnv &env = inflate_env();
+    InflateIn in{};
+    in.n = n;
+    in.max_len = max_len;
+    in.cus = (uint64_t)ctx->cus;
+    in.latency = latency;
+    in.need_hbm = need_hbm;
+    in.dict_len = ctx->dict_id ? ctx->dict_len : 0u;
+    in.wave_only = env.wave_only;
+    in.no_order = env.no_order;
+    in.no_rec = env.no_rec;
+    in.rec_per_cu_4k = (uint64_t)ctx->rec_per_cu[0];
+    in.rec_per_cu_1k = (uint64_t)ctx->rec_per_cu[1];
+    in.chunk_per_cu = (uint64_t)ctx->chunk_per_cu;
+    in.rec_max = kRecMax;
+    in.rec_out_max = kRecOutMax;
+    in.scan_block = kIdxScanBlock;
+    in.out_limit = kInflateLdsOut;
+    return in;
+}
+
+// Each stage gets the InflateArgs of the call, `a`, and launches with it or with a copy that carries the
+// fields only its own launches see.  A field a stage sets on `a` itself stays for the launches after it.
+
+// The visit order: member indices by compressed length into ctx->order (bins | indices).
+static int stage_order(pmc_ctx *ctx, const InflatePlan &P, const uint32_t *src_len, uint64_t n, const uint32_t **ord,
+                       hipStream_t st) {
+    uint32_t *bins = (uint32_t *)ctx->order.p, *o = bins + kOrderBins;
+    HIP_TRY(hipMemsetAsync(bins, 0, kOrderBins * 4, st));
     klaunch(ctx, PMC_K_ORDER, st, [&] {
-        hipLaunchKernelGGL(inflate_chunk_scan_kernel, dim3(mb), dim3(256), 0, st, a, X);
-        r = scan_u32(X.cnt, nullptr, (uint32_t)n, (uint64_t *)(p + o_pre), bsum, st);
+        hipLaunchKernelGGL(order_hist_kernel, dim3(P.ob), dim3(256), 0, st, src_len, n, bins);
+        hipLaunchKernelGGL(order_scan_kernel, dim3(1), dim3(1024), 0, st, bins);
+        hipLaunchKernelGGL(order_scatter_kernel, dim3(P.ob), dim3(256), 0, st, src_len, n, bins, o);
+    });
+    *ord = o;
+    return PMC_OK;
+}
+
+// The record kernel; the record rows it sets on `a` stay.  It appends the members it leaves to the lane passes
+// to the list in ctx->bigl (count | members).
+static int stage_record(pmc_ctx *ctx, const InflatePlan &P, InflateArgs &a, const uint32_t *ord, hipStream_t st) {
+    a.rec_group = P.G;
+    a.rec_max_out = P.rec_max_out;
+    a.rec_work = (uint32_t *)ctx->recs.p;
+    a.rec_scratch = (uint32_t *)((uint8_t *)ctx->recs.p + 256);
+    a.rec_stride = P.rstride;
+#if defined(PMC_STAMPS) || defined(PMC_PHASE_STOP)
+    if (const char *e = getenv("PMC_STOP_AFTER")) a.stop_after = atoi(e); // 31 prepare, 32 phase A
+#endif
+    HIP_TRY(hipMemsetAsync(a.rec_work, 0, 4, st));
+    InflateArgs k = a;
+    k.order = ord;
+    k.big_count = (uint32_t *)ctx->bigl.p;
+    k.big_list = (uint32_t *)((uint8_t *)ctx->bigl.p + 256);
+    HIP_TRY(hipMemsetAsync(k.big_count, 0, 4, st));
+    klaunch(ctx, PMC_K_INFLATE_REC, st, [&] {
+        hipLaunchKernelGGL(rec_kernel(P.out1k), dim3(P.rb), dim3(64), rec_lds_bytes(P.rec_max_out), st, k);
+    });
+    return PMC_OK;
+}
+
+// The lane passes: over the record kernel's list when it ran, else over every member.  multi_pass stays on `a`.
+static void stage_lanes(pmc_ctx *ctx, const InflatePlan &P, InflateArgs &a, const uint32_t *ord, hipStream_t st) {
+    a.multi_pass = P.multi_pass ? 1 : 0;
+    InflateArgs k = a;
+    k.order = ord;
+    if (P.rec) {
+        k.big_only = 1;
+        k.big_count = (uint32_t *)ctx->bigl.p;
+        k.big_list = (uint32_t *)((uint8_t *)ctx->bigl.p + 256);
+    }
+    klaunch(ctx, PMC_K_INFLATE_LANE, st, [&] {
+        hipLaunchKernelGGL((inflate_lane_kernel<kLaneLitCap, false>), dim3(P.lb), dim3(64), kLaneLdsBytes, st, k);
+        // members whose lit/len code did not fit its lists (a third of 30 KB JSON values): the wide
+        // instance (it skips every other member at once)
+        hipLaunchKernelGGL((inflate_lane_kernel<kLaneWideLit, false>), dim3(P.lb), dim3(64), kLaneWideLdsBytes, st, k);
+        if (P.multi_pass)
+            hipLaunchKernelGGL((inflate_lane_kernel<kLaneWideLit, true>), dim3(P.lb), dim3(64), kLaneMultiLdsBytes, st, k);
+    });
+}
+
+// ---- indexed members (pmc_inflate_chunk.hip; include/pmc_codec.h "member index") --------------------------
+// The chunk pass up to the CRC check: which members carry a valid index (InflatePlan::chunk_all), a prefix sum
+// of their chunk counts, one lane per chunk, then rc / dst_len / crc_expect of the members whose chunks all
+// decoded.  Enqueue only, no readback; the rows in ctx->idx are O(n).  The caller runs inflate_verify_kernel,
+// then chunk_pass_count.
+static int chunk_pass_decode(pmc_ctx *ctx, const InflatePlan &P, const InflateArgs &a, ChunkArgs &X, hipStream_t st) {
+    uint8_t *p = (uint8_t *)ctx->idx.p;
+    uint64_t *pre = (uint64_t *)(p + P.idx.pre), *bsum = (uint64_t *)(p + P.idx.bsum);
+    X.cnt = (uint32_t *)(p + P.idx.cnt);
+    X.fail = (uint32_t *)(p + P.idx.fail);
+    X.pre = pre;
+    X.total = (uint64_t *)(p + P.idx.total);
+    X.counts = (uint64_t *)((uint8_t *)ctx->guard.p + 32);
+    X.all = P.chunk_all ? 1 : 0;
+    int r = PMC_OK;
+    klaunch(ctx, PMC_K_ORDER, st, [&] {
+        hipLaunchKernelGGL(inflate_chunk_scan_kernel, dim3(P.mb), dim3(256), 0, st, a, X);
+        r = scan_u32(X.cnt, nullptr, (uint32_t)a.n, pre, bsum, st);
     });
     if (r) return r; // (scan_u32 has named the launch that failed)
-    // (the item count stays on the device: a grid of the resident waves strides over the items, and returns
-    // at once when there are none)
-    // (asked once per context, under its decompress lock: a context is one device)
-    if (!ctx->chunk_per_cu) ctx->chunk_per_cu = occupancy_blocks((const void *)inflate_chunk_kernel, 64, kChunkLdsBytes);
-    const unsigned cb =
-        (unsigned)std::min<uint64_t>((uint64_t)ctx->cus * ctx->chunk_per_cu, (n * kIdxMaxChunks + 63) / 64);
     klaunch(ctx, PMC_K_INFLATE_LANE, st, [&] {
-        hipLaunchKernelGGL(inflate_chunk_kernel, dim3(cb), dim3(64), kChunkLdsBytes, st, a, X);
-        hipLaunchKernelGGL(inflate_chunk_finish_kernel, dim3(mb), dim3(256), 0, st, a, X);
+        hipLaunchKernelGGL(inflate_chunk_kernel, dim3(P.cb), dim3(64), kChunkLdsBytes, st, a, X);
+        hipLaunchKernelGGL(inflate_chunk_finish_kernel, dim3(P.mb), dim3(256), 0, st, a, X);
     });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -1174,10 +1254,27 @@ static int chunk_pass_decode(pmc_ctx *ctx, const InflateArgs &a, ChunkArgs &X, b
     }
     return PMC_OK;
 }
-static void chunk_pass_count(pmc_ctx *ctx, const InflateArgs &a, const ChunkArgs &X, hipStream_t st) {
-    const unsigned mb = (unsigned)std::min<uint64_t>((a.n + 255) / 256, (uint64_t)ctx->cus * 8);
+static void chunk_pass_count(pmc_ctx *ctx, const InflatePlan &P, const InflateArgs &a, const ChunkArgs &X, hipStream_t st) {
     klaunch(ctx, PMC_K_INFLATE_LANE, st,
-            [&] { hipLaunchKernelGGL(inflate_chunk_count_kernel, dim3(mb), dim3(256), 0, st, a, X); });
+            [&] { hipLaunchKernelGGL(inflate_chunk_count_kernel, dim3(P.mb), dim3(256), 0, st, a, X); });
+}
+
+// Launches a wave-per-member kernel (blocks of wpb waves) and checks the launch under `name`.
+static int launch_wave(pmc_ctx *ctx, int kind, InflateKernel k, unsigned blocks, int wpb, size_t lds, const InflateArgs &a,
+                       const char *name, hipStream_t st) {
+    klaunch(ctx, kind, st, [&] { hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * wpb), lds, st, a); });
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_err(name, e);
+        return PMC_E_NO_DEVICE;
+    }
+    return PMC_OK;
+}
+// An LDS wave pass with the image and input sizes in `a`; its wave_bytes follow them.
+static int wave_lds(pmc_ctx *ctx, InflateKernel k, InflateArgs &a, const char *name, hipStream_t st) {
+    a.wave_bytes = inflate_wave_bytes(false, a.dict_out, a.lds_max_in);
+    const Launch L = plan_lds(ctx, (const void *)k, a.wave_bytes, a.n);
+    return launch_wave(ctx, PMC_K_INFLATE_LDS, k, (unsigned)L.blocks, L.wpb, L.lds, a, name, st);
 }
 
 static int decompress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t *src_off,
@@ -1187,208 +1284,80 @@ static int decompress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_
     if (!ctx) return PMC_E_ARG;
     if (n == 0) return PMC_OK;
     hipStream_t st = (hipStream_t)stream;
-    InflateArgs a{src, src_off, src_len, dst, dst_off, dst_cap, dst_len, rc, n, 0, 0, 0, nullptr, ctx->dbg ? ctx->dbg + 16 : nullptr,
-                  nullptr, 0};
+    const InflateIn in = inflate_in(ctx, n, max_len, latency, need_hbm);
+    const InflatePlan P = plan_inflate(in);
+    int r;
+    if (P.verify && (r = ctx->crcx.ensure(P.crcx_bytes))) return r;
+    if (P.order && (r = ctx->order.ensure(P.order_bytes))) return r;
+    if (P.rec && ((r = ctx->recs.ensure(P.recs_bytes)) || (r = ctx->bigl.ensure(P.bigl_bytes)))) return r;
+    if (P.chunk_pass && (r = ctx->idx.ensure(P.idx.bytes))) return r;
+    // what every launch of the call sees
+    InflateArgs a{};
+    a.src = src;
+    a.src_off = src_off;
+    a.src_len = src_len;
+    a.dst = dst;
+    a.dst_off = dst_off;
+    a.dst_cap = dst_cap;
+    a.dst_len = dst_len;
+    a.rc = rc;
+    a.n = n;
+    a.dbg = ctx->dbg ? ctx->dbg + 16 : nullptr;
     // (a context with a dictionary: the record and lane kernels leave its dictionary members to the LDS wave
     // kernel, which decodes them behind the dictionary)
-    const uint32_t dD = ctx->dict_id ? ctx->dict_len : 0u;
+    const uint32_t dD = in.dict_len;
     a.dict = dD ? (const uint8_t *)ctx->dict.p : nullptr;
     a.dict_len = dD;
     a.dict_id = dD ? ctx->dict_id : 0u;
-    // lane-per-member fast path (pmc_inflate_lane.hip), then the CRC check; whatever it
-    // declines (rc = kInflateRetry) goes through the wave-per-member kernels below
-    // (PMC_INFLATE_WAVE=1: everything through the wave kernels).
-    static const bool wave_only = getenv("PMC_INFLATE_WAVE") && atoi(getenv("PMC_INFLATE_WAVE"));
-    // (round 4 measured routing batches of <= 2048 members to the wave kernels instead: 256 x 4 KiB took
-    // 12.5 ms there against 3.2 ms for 4096 members through the lane / record paths -- not done)
-    // The chunk pass over indexed members runs in every call that may hold one (a member of more than one
-    // chunk decodes to more than kIdxChunk bytes), on either route; with PMC_INFLATE_WAVE=1 it is off, like
-    // the other fast paths.  A call with max_len <= kIdxChunk launches nothing for it.
-    const bool chunk_pass = !wave_only && max_len > kIdxChunk;
-    ChunkArgs X{};
-    auto verify = [&] { // CRC-32 of every member the lane decoders finished (rc 0)
-        // (members per wave as for the record kernel: a small batch takes one wave per member)
-        uint32_t VG = 1;
-        while (VG < 64 && ((uint64_t)n + VG - 1) / VG > (uint64_t)ctx->cus * 32) VG *= 2;
-        a.verify_group = VG;
-        const unsigned vb = (unsigned)std::min<uint64_t>(((uint64_t)n + 8ull * VG - 1) / (8ull * VG), (uint64_t)ctx->cus * 4);
-        klaunch(ctx, PMC_K_INFLATE_VERIFY, st,
-                [&] { hipLaunchKernelGGL(inflate_verify_kernel, dim3(vb), dim3(512), 0, st, a); });
+    if (P.verify) a.crc_expect = (uint32_t *)ctx->crcx.p;
+    // the stages before the wave kernels also see the visit order
+    const uint32_t *ord = nullptr;
+    auto ordered = [&] {
+        InflateArgs k = a;
+        k.order = ord;
+        return k;
     };
-    if (chunk_pass && latency) {
-        // the wave-only route (a small batch, or at most 4 members per CU -- where 1000 x 1 MiB lands): the
-        // chunk pass takes the indexed members, marks every other one kInflateRetry, and the wave kernels
-        // below run retry_only (uncounted: pmc_ctx_guard_counts counts[4] is the pipeline route's)
-        int r = ctx->crcx.ensure((uint64_t)n * 4);
-        if (r) return r;
-        a.crc_expect = (uint32_t *)ctx->crcx.p;
-        r = chunk_pass_decode(ctx, a, X, true, st);
-        if (r) return r;
-        verify();
-        chunk_pass_count(ctx, a, X, st);
-        a.retry_only = 1;
+    if (P.order && (r = stage_order(ctx, P, src_len, n, &ord, st))) return r;
+    if (P.rec && (r = stage_record(ctx, P, a, ord, st))) return r;
+    if (P.lane_route) stage_lanes(ctx, P, a, ord, st);
+    // indexed members (FLG = FEXTRA: the lane passes declined them), one lane per chunk
+    ChunkArgs X{};
+    if (P.chunk_pass && (r = chunk_pass_decode(ctx, P, ordered(), X, st))) return r;
+    if (P.verify) { // CRC-32 of every member the lane decoders and the chunk pass finished (rc 0)
+        a.verify_group = P.VG;
+        const InflateArgs k = ordered();
+        klaunch(ctx, PMC_K_INFLATE_VERIFY, st,
+                [&] { hipLaunchKernelGGL(inflate_verify_kernel, dim3(P.vb), dim3(512), 0, st, k); });
     }
-    if (!wave_only && !latency) {
-        int r = ctx->crcx.ensure((uint64_t)n * 4);
-        if (r) return r;
-        a.crc_expect = (uint32_t *)ctx->crcx.p;
-        // visit order by compressed length (PMC_INFLATE_ORDER=0: index order)
-        static const bool no_order = getenv("PMC_INFLATE_ORDER") && !atoi(getenv("PMC_INFLATE_ORDER"));
-        if (!no_order && n >= 4096) {
-            r = ctx->order.ensure((uint64_t)kOrderBins * 4 + (uint64_t)n * 4);
-            if (r) return r;
-            uint32_t *bins = (uint32_t *)ctx->order.p, *ord = bins + kOrderBins;
-            HIP_TRY(hipMemsetAsync(bins, 0, kOrderBins * 4, st));
-            const unsigned ob = (unsigned)std::min<uint64_t>(((uint64_t)n + 1023) / 1024, (uint64_t)ctx->cus * 4);
-            klaunch(ctx, PMC_K_ORDER, st, [&] {
-                hipLaunchKernelGGL(order_hist_kernel, dim3(ob), dim3(256), 0, st, src_len, (uint64_t)n, bins);
-                hipLaunchKernelGGL(order_scan_kernel, dim3(1), dim3(1024), 0, st, bins);
-                hipLaunchKernelGGL(order_scatter_kernel, dim3(ob), dim3(256), 0, st, src_len, (uint64_t)n, bins, ord);
-            });
-            a.order = ord;
-        }
-        // members of <= kRecOutMax output bytes: the two-phase record kernel, one block per
-        // resident wave (each block owns 64 record rows); larger ones: the lane kernel
-        static const bool no_rec = getenv("PMC_INFLATE_REC") && !atoi(getenv("PMC_INFLATE_REC"));
-        const unsigned lb = (unsigned)std::min<uint64_t>(((uint64_t)n + 63) / 64, (uint64_t)ctx->cus * 16);
-        if (!no_rec) {
-            const uint32_t rstride =
-                (uint32_t)std::min<uint64_t>(kRecMax, std::max<uint64_t>(64, ((uint64_t)max_len + 63) & ~(uint64_t)63));
-            // the 1 KiB image instance when no member may decode to more (max_len: the largest capacity),
-            // else the 4 KiB one
-            const bool out1k = max_len <= 1024;
-            const InflateKernel rk = rec_kernel(out1k);
-            const uint32_t rlds = rec_lds_bytes(out1k ? 1024 : kRecOutMax);
-            // exactly the resident blocks: a block owns its rows for the whole grid-stride loop,
-            // and blocks beyond residency would start only when the first ones have finished
-            static int rec_per_cu_k[2] = {0, 0};
-            int &rec_per_cu = rec_per_cu_k[out1k ? 1 : 0];
-            if (!rec_per_cu) {
-                int nb = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)rk, 64, rlds) != hipSuccess || nb < 1)
-                    nb = (int)(kLdsPerCu / rlds);
-                rec_per_cu = nb;
-            }
-            // members per grab: the smallest power of two whose grabs fit the resident blocks once, so a small
-            // batch (a server's few hundred GETs) spreads one or a few members per wave instead of 64 on a few
-            // CUs with phase B's member-serial loop exposed
-            const uint64_t slots = (uint64_t)ctx->cus * rec_per_cu;
-            uint32_t G = 1;
-            while (G < 64 && ((uint64_t)n + G - 1) / G > slots) G *= 2;
-            a.rec_group = G;
-            const unsigned rb = (unsigned)std::min<uint64_t>(((uint64_t)n + G - 1) / G, slots);
-            a.rec_max_out = out1k ? 1024u : kRecOutMax;
-            r = ctx->recs.ensure((uint64_t)rb * 64 * rstride * 4 + 256);
-            if (r) return r;
-            a.rec_work = (uint32_t *)ctx->recs.p;
-            a.rec_scratch = (uint32_t *)((uint8_t *)ctx->recs.p + 256);
-            HIP_TRY(hipMemsetAsync(a.rec_work, 0, 4, st));
-            r = ctx->bigl.ensure((uint64_t)n * 4 + 256);
-            if (r) return r;
-            a.big_count = (uint32_t *)ctx->bigl.p;
-            a.big_list = (uint32_t *)((uint8_t *)ctx->bigl.p + 256);
-            HIP_TRY(hipMemsetAsync(a.big_count, 0, 4, st));
-            a.rec_stride = rstride;
-#if defined(PMC_STAMPS) || defined(PMC_PHASE_STOP)
-            if (const char *e = getenv("PMC_STOP_AFTER")) a.stop_after = atoi(e); // 31 prepare, 32 phase A
-#endif
-            klaunch(ctx, PMC_K_INFLATE_REC, st, [&] { hipLaunchKernelGGL(rk, dim3(rb), dim3(64), rlds, st, a); });
-            a.big_only = 1;
-        }
-        // members of several blocks exist only above 16383 output bytes (zlib flushes every 16383
-        // symbols): then a third pass decodes them block after block
-        a.multi_pass = max_len > 16383 ? 1 : 0;
-        klaunch(ctx, PMC_K_INFLATE_LANE, st, [&] {
-            hipLaunchKernelGGL((inflate_lane_kernel<kLaneLitCap, false>), dim3(lb), dim3(64), kLaneLdsBytes, st, a);
-            // members whose lit/len code did not fit its lists (a third of 30 KB JSON values): the wide
-            // instance (it skips every other member at once)
-            hipLaunchKernelGGL((inflate_lane_kernel<kLaneWideLit, false>), dim3(lb), dim3(64), kLaneWideLdsBytes, st, a);
-            if (a.multi_pass)
-                hipLaunchKernelGGL((inflate_lane_kernel<kLaneWideLit, true>), dim3(lb), dim3(64), kLaneMultiLdsBytes, st,
-                                   a);
-        });
-        a.big_only = 0;
-        a.big_list = nullptr;
-        a.big_count = nullptr;
-        // indexed members (FLG = FEXTRA: the lane passes declined them), one lane per chunk
-        if (chunk_pass) {
-            r = chunk_pass_decode(ctx, a, X, false, st);
-            if (r) return r;
-        }
-        verify();
-        if (chunk_pass) chunk_pass_count(ctx, a, X, st);
-        a.retry_only = 1;
-        a.retried = (uint32_t *)ctx->guard.p + 4; // (pmc_ctx_guard_counts counts[4])
-        a.order = nullptr;
-    }
-    // output image capacity for the LDS kernel; the compressed input of a member whose
-    // output fits is at most gzip_bound(out) unless it is not a deflate member at all
-    uint64_t out_cap = std::min<uint64_t>(inflate_lds_out_limit(), std::max<uint64_t>(max_len, 1));
-    out_cap = (out_cap + 63) & ~(uint64_t)63;
-    a.lds_max_out = out_cap;
-    a.lds_max_in = gzip_bound(out_cap) + 64;
-    // (the image: the dictionary, rounded to 16 bytes, in front of the plain members' out_cap bytes.  A
-    // dictionary member starts at the image's first byte and needs dD + min(capacity, ISIZE) of it: that fits
-    // while its capacity is within max_len, which a device-resident caller need not keep -- max_len bounds the
-    // decompressed sizes, a slab passes its own.  The members this pass cannot hold go to a second launch sized
-    // for the longest dictionary member, dD + ISIZE = 16382; like the HBM variant it is always launched, the
-    // lengths being device-resident, unless this pass has that size already or a host-memory caller, who
-    // knows lengths and capacities, says that no member needs it.)
-    a.dict_out = (uint32_t)(out_cap + ((dD + 15u) & ~15u));
-    const uint64_t dict_in = dD ? gzip_bound(kDictSpan - dD) + 64 : 0;
-    const bool dict_second = dD && need_hbm && (a.dict_out < kDictSpan || a.lds_max_in < dict_in);
+    if (P.chunk_pass) chunk_pass_count(ctx, P, ordered(), X, st);
+    // ---- wave-per-member kernels: every member, or those the stages above left kInflateRetry ----
+    a.retry_only = P.retry_only ? 1 : 0;
+    if (P.count_retried) a.retried = (uint32_t *)ctx->guard.p + 4; // (pmc_ctx_guard_counts counts[4])
+    a.lds_max_out = P.out_cap;
+    a.lds_max_in = P.lds_max_in;
+    a.dict_out = P.dict_out;
     a.dict_pass = 0;
-    a.dict_last = dict_second ? 0u : 1u;
-    {
-        uint64_t wb = inflate_wave_bytes(false, a.dict_out, a.lds_max_in);
-        const InflateKernel lk = wave_kernel(false, dD != 0);
-        Launch L = plan_lds(ctx, (const void *)lk, wb, n);
-        a.wave_bytes = wb;
-        klaunch(ctx, PMC_K_INFLATE_LDS, st,
-                [&] { hipLaunchKernelGGL(lk, dim3(L.blocks), dim3(64 * L.wpb), L.lds, st, a); });
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            set_err("inflate_kernel<lds>", e);
-            return PMC_E_NO_DEVICE;
-        }
-    }
-    if (dict_second) {
+    a.dict_last = P.dict_second ? 0u : 1u;
+    if ((r = wave_lds(ctx, wave_kernel(false, dD != 0), a, "inflate_kernel<lds>", st))) return r;
+    if (P.dict_second) {
         InflateArgs a2 = a;
         a2.dict_pass = 1;
         a2.dict_last = 1;
-        a2.first_img = a.dict_out;
-        a2.first_in = (uint32_t)a.lds_max_in;
-        a2.lds_max_out = (kDictSpan + 63) & ~63u;
-        a2.dict_out = (uint32_t)a2.lds_max_out;
-        a2.lds_max_in = dict_in;
-        a2.wave_bytes = inflate_wave_bytes(false, a2.dict_out, a2.lds_max_in);
-        const InflateKernel lk = wave_kernel(false, true);
-        Launch L = plan_lds(ctx, (const void *)lk, a2.wave_bytes, n);
-        klaunch(ctx, PMC_K_INFLATE_LDS, st,
-                [&] { hipLaunchKernelGGL(lk, dim3(L.blocks), dim3(64 * L.wpb), L.lds, st, a2); });
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            set_err("inflate_dict_kernel<lds>", e);
-            return PMC_E_NO_DEVICE;
-        }
+        a2.first_img = P.second.first_img;
+        a2.first_in = P.second.first_in;
+        a2.lds_max_out = P.second.lds_max_out;
+        a2.dict_out = P.second.dict_out;
+        a2.lds_max_in = P.second.lds_max_in;
+        if ((r = wave_lds(ctx, wave_kernel(false, true), a2, "inflate_dict_kernel<lds>", st))) return r;
     }
     // members whose output or input exceeds the LDS image (rare: large values, or garbage
     // input longer than its ISIZE suggests) -> HBM variant; always launched because input
     // lengths are device-resident (the kernel skips members the LDS kernel handled) -- unless a
     // host-memory caller, who knows the lengths, says no member needs it
-    if (need_hbm) {
-        uint64_t wb = inflate_wave_bytes(true, 0, 0);
-        uint64_t waves = std::min<uint64_t>((uint64_t)ctx->cus * 4, n);
-        a.wave_bytes = wb;
-        klaunch(ctx, PMC_K_INFLATE_HBM, st, [&] {
-            hipLaunchKernelGGL(wave_kernel(true, dD != 0), dim3((unsigned)((waves + 3) / 4)), dim3(256),
-                               kCrcTabBytes + 4 * wb, st, a);
-        });
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            set_err("inflate_kernel<hbm>", e);
-            return PMC_E_NO_DEVICE;
-        }
+    if (P.hbm) {
+        a.wave_bytes = inflate_wave_bytes(true, 0, 0);
+        return launch_wave(ctx, PMC_K_INFLATE_HBM, wave_kernel(true, dD != 0), P.hbm_blocks, 4, kCrcTabBytes + 4 * a.wave_bytes,
+                           a, "inflate_kernel<hbm>", st);
     }
     return PMC_OK;
 }
@@ -1423,17 +1392,9 @@ PMC_API int pmc_gzip_decompress_batch(pmc_ctx *ctx, const uint8_t *src, const ui
     std::lock_guard<std::recursive_mutex> dir_lock(ctx->dir_mu[1]);
     int r = dir_enter(ctx, 1, st);
     if (r) return r;
-    // a server-sized GET batch (<= 4,096 members, capacities within the wave kernel's LDS image and
-    // <= 16 MiB of output in all, the host calls' limits): the wave-per-member kernel alone (whole-wave
-    // Huffman decode per member instead of one lane's; 400 x 4 KiB: 1.47 -> ~0.5 ms, round 5), then the
-    // HBM variant for anything it declined (the lengths are device-resident)
-    // A batch of at most 4 members per CU also takes the wave kernels whatever its sizes: one wave per
-    // member beats one lane per member until the lanes' density pays (1000 x 1 MiB: 220 ms against 453 ms
-    // through the multi-block lane pass; 40K x 64 KiB: 542 ms against 25 ms -- round 5, same box).
-    // (PMC_LATENCY_BATCH=0 turns both clauses off, so A/B runs and fault tests can still reach the lane /
-    // record pipeline with small batches -- ADVICE r5)
-    const bool small = latency_decompress(n, max_len, (uint64_t)n * max_len) ||
-                       (latency_batch() != 0 && (uint64_t)n <= 4ull * ctx->cus);
+    // (a server-sized GET batch, or at most 4 members per CU: the wave-only route)
+    const bool small = inflate_latency(n, max_len, (uint64_t)n * max_len, ctx->cus, latency_batch(), latency_max_len(),
+                                       true, kInflateLdsOut);
     r = decompress_batch_body(ctx, src, src_off, src_len, n, dst, dst_off, dst_cap, dst_len, rc, max_len, stream, small,
                               true);
     const int r2 = dir_leave(ctx, 1, st);
@@ -1605,15 +1566,16 @@ int host_batch_locked(pmc_ctx *ctx, Dir dir, const uint8_t *src, const uint64_t 
     // Routing (limits measured with scripts/few_sweep.py).  Compress: up to 1,024 values of <= 4 KiB the
     // one-kernel path (deflate_small_kernel) beats the pipeline; above 4 KiB the wave-per-value kernel would
     // work from HBM, far slower than the split pipeline's large pass.  Decompress: the wave-per-member
-    // inflate kernel holds a member's output in LDS up to inflate_lds_out_limit() (48 KiB), so a member up
+    // inflate kernel holds a member's output in LDS up to kInflateLdsOut (48 KiB), so a member up
     // to that size stays on the latency path (a 30 KB member: 0.81 ms there against 3.8 ms through the
-    // pipeline); its batch limit is 4,096 members / 16 MiB of output (latency_decompress:
+    // pipeline); its batch limit is 4,096 members / 16 MiB of output (inflate_latency:
     // round 5 measured the wave kernel still 2x ahead there).
     const uint64_t lat_max = latency_max_len(), lat_batch = latency_batch();
     // (a fast-level compress always takes the pipeline: the one-kernel path is exact only)
     const bool fast = dir == kCompress && level_is_fast(ctx->level) && ctx->lane_order_ok;
     const bool latency = !force_pipeline && (dir == kCompress ? !fast && n <= lat_batch && max_len <= lat_max
-                                                              : latency_decompress(n, max_len, out_bytes));
+                                                              : inflate_latency(n, max_len, out_bytes, ctx->cus, lat_batch,
+                                                                                lat_max, false, kInflateLdsOut));
     ctx->path_calls[(latency ? 0 : 2) + (dir == kCompress ? 0 : 1)]++;
     // The latency path's kernel reads its inputs from, and writes its outputs to, coherent host memory in
     // place: no H2D / D2H copies (each a runtime copy kernel of its own) around its one launch.
@@ -1681,8 +1643,7 @@ int host_batch_locked(pmc_ctx *ctx, Dir dir, const uint8_t *src, const uint64_t 
             else  // the wave kernels' HBM variant only for members the LDS image cannot hold
                 e = decompress_batch_body(ctx, d_src, d_soff, d_slen, n, d_dst, d_doff, d_dcap, d_dlen, d_rc,
                                           (uint32_t)max_len, st, lat,
-                                          !lat || max_len > inflate_lds_limit_out(max_len) ||
-                                              max_in > gzip_bound(inflate_lds_limit_out(max_len)) + 64);
+                                          inflate_need_hbm(lat, max_len, max_in, kInflateLdsOut));
             const int e2 = dir_leave(ctx, d, st);
             if (!e) e = e2;
         }

@@ -4,7 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "pmc_plan.hpp" // kLvSeg / kLvOverlap / kLvChunk, the chunk-array row counts, kOrderBins, kDictSpan
+#include "pmc_plan.hpp" // kLvSeg / kLvOverlap / kLvChunk, the chunk-array row counts, kOrderBins, kDictSpan, gzip_bound
 
 namespace pmc {
 
@@ -15,12 +15,6 @@ constexpr int PMC_E_CAPACITY_DEV = -101;
 constexpr int PMC_E_ARG_DEV = -102;
 
 constexpr uint32_t kSlabSyms = 16384; // per-wave symbol slab (>= 16383 symbols per block)
-
-// Worst case gzip member size (same formula as oracle_gzip_bound): stored fallback adds
-// 5 B per 16383-symbol block; after a window slide fixed/dynamic blocks stay <= 9/8 len.
-__host__ __device__ inline uint64_t gzip_bound(uint64_t len) {
-    return len + (len >> 3) + 6 * (len / 16383 + 1) + 32;
-}
 
 struct DeflateArgs {
     const uint8_t *src;

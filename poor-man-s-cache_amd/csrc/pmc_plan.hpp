@@ -1,7 +1,9 @@
 // pmc_plan.hpp -- the host-side planning arithmetic of a compress call: which path claims which lengths
 // (Route), where the split pipeline's chunk arrays lie (SplitLayout) and how the large values are cut
-// into rounds (LvRound).  Plain C++17 with no HIP in it: pmc_capi.hip turns these plans into launches,
-// and tests/host/plan_check.cpp prints them for tests/test_host_plan.py, which needs no GPU.
+// into rounds (LvRound); and of a decompress call: which route it takes (inflate_latency), which stages
+// run and every grid, group and scratch size of them (InflatePlan).  Plain C++17 with no HIP in it:
+// pmc_capi.hip turns these plans into launches, and tests/host/plan_check.cpp prints them for
+// tests/test_host_plan.py, which needs no GPU.
 #pragma once
 #include <stdint.h>
 
@@ -385,6 +387,199 @@ inline Route plan_route(const RouteIn &in) {
     R.hbm_waves = std::min<uint64_t>(R.hbm_waves, n);
     R.rlist = R.gated && R.hbm_waves;
     return R;
+}
+
+// ---- the decompress plan ---------------------------------------------------------------------------------
+// Worst case gzip member size (same formula as oracle_gzip_bound): stored fallback adds
+// 5 B per 16383-symbol block; after a window slide fixed/dynamic blocks stay <= 9/8 len.
+PMC_HD inline uint64_t gzip_bound(uint64_t len) { return len + (len >> 3) + 6 * (len / 16383 + 1) + 32; }
+
+// The one statement of the wave-only route: the batches that go through the wave-per-member kernels alone
+// instead of the lane / record pipeline (InflateIn::latency).  lat_batch / lat_max_len: the compress side's
+// latency limits (1,024 values of 4 KiB; PMC_LATENCY_BATCH / PMC_LATENCY_MAX_LEN, 0 disables the path);
+// out_limit: the LDS wave kernel's output image (48 KiB), the decompress side's length limit.  A host call
+// passes the sum of its capacities as out_bytes, the device-resident entry n * max_len.
+// The batch limit is 4x the compress side's, with at most 4x the output in all (4,096 x 4 KiB members: 0.81 ms
+// device-resident through the wave kernel against 1.69 ms through the pipeline; compress at 4,096 x 4 KiB is
+// faster through the pipeline, 2.86 against 3.33 ms -- round 5, same box).
+// device_call: a server-sized GET batch (<= 4,096 members, capacities within the wave kernel's LDS image and
+// <= 16 MiB of output in all, the host calls' limits) takes the wave-per-member kernel alone there too
+// (whole-wave Huffman decode per member instead of one lane's; 400 x 4 KiB: 1.47 -> ~0.5 ms, round 5), then
+// the HBM variant for anything it declined (the lengths are device-resident).  A device-resident batch of at
+// most 4 members per CU also takes the wave kernels whatever its sizes: one wave per member beats one lane
+// per member until the lanes' density pays (1000 x 1 MiB: 220 ms against 453 ms through the multi-block lane
+// pass; 40K x 64 KiB: 542 ms against 25 ms -- round 5, same box).  (PMC_LATENCY_BATCH=0 turns both clauses
+// off, so A/B runs and fault tests can still reach the lane / record pipeline with small batches -- ADVICE r5)
+inline bool inflate_latency(uint64_t n, uint64_t max_len, uint64_t out_bytes, uint64_t cus, uint64_t lat_batch,
+                            uint64_t lat_max_len, bool device_call, uint64_t out_limit) {
+    const uint64_t lb = 4 * lat_batch, lm = lat_max_len;
+    const uint64_t max_out = lm ? std::max(lm, out_limit) : 0;
+    if (n <= lb && max_len <= max_out && (max_len <= lm || out_bytes <= lb * lm)) return true;
+    return device_call && lat_batch != 0 && n <= 4 * cus;
+}
+
+struct InflateIn {
+    uint64_t n, max_len;  // members in the batch (>= 1); the caller's bound on their decompressed sizes
+    uint64_t cus;
+    bool latency;         // the wave-only route (inflate_latency)
+    bool need_hbm;        // false: a host-memory caller says no member needs more than the LDS pass (inflate_need_hbm)
+    uint32_t dict_len;    // the context's dictionary (0: it has no dictionary id)
+    bool wave_only, no_order, no_rec; // PMC_INFLATE_WAVE=1, PMC_INFLATE_ORDER=0, PMC_INFLATE_REC=0
+    // resident blocks per CU, as the runtime says: inflate_rec_kernel<1024>, <kRecOutMax>, inflate_chunk_kernel
+    uint64_t rec_per_cu_1k, rec_per_cu_4k, chunk_per_cu;
+    // the kernels' own constants: kRecMax, kRecOutMax, scan_u32's block (1024), the LDS wave kernel's largest
+    // output image (48 KiB)
+    uint64_t rec_max, rec_out_max, scan_block, out_limit;
+};
+
+// Which stages of a decompress call run, with their grids, groups and scratch sizes.  Grids and sizes are
+// stated for every call, whether or not the stage they belong to runs.
+struct InflatePlan {
+    // lane_route: the lane-per-member fast paths (order, record, lane passes), then the CRC check; whatever
+    // they decline (rc = kInflateRetry) goes through the wave-per-member kernels.  Off on the wave-only route
+    // and with PMC_INFLATE_WAVE=1 (everything through the wave kernels).
+    // (round 4 measured routing batches of <= 2048 members to the wave kernels instead: 256 x 4 KiB took
+    // 12.5 ms there against 3.2 ms for 4096 members through the lane / record paths -- not done)
+    bool lane_route;
+    // The chunk pass over indexed members runs in every call that may hold one (a member of more than one
+    // chunk decodes to more than kIdxChunk bytes), on either route; with PMC_INFLATE_WAVE=1 it is off, like
+    // the other fast paths.  A call with max_len <= kIdxChunk launches nothing for it.
+    // chunk_all: the wave-only route (a small batch, or at most 4 members per CU -- where 1000 x 1 MiB lands):
+    // the pass looks at every member, takes the indexed ones and marks every other one kInflateRetry; on the
+    // lane route it looks at those the lane passes left kInflateRetry.
+    bool chunk_pass, chunk_all;
+    bool order;       // visit order by compressed length (PMC_INFLATE_ORDER=0: index order)
+    // members of <= rec_max_out output bytes: the two-phase record kernel, one block per resident wave (each
+    // block owns 64 record rows); larger ones: the lane kernel (PMC_INFLATE_REC=0: all of them)
+    bool rec;
+    // members of several blocks exist only above 16383 output bytes (zlib flushes every 16383 symbols): then
+    // a third lane pass decodes them block after block
+    bool multi_pass;
+    bool verify;      // the CRC check of the members the lane decoders and the chunk pass finished
+    bool dict_second; // the second LDS pass, sized for the longest dictionary member (below)
+    bool hbm;         // the wave kernels' HBM variant
+    // the wave kernels take only members a stage before them marked kInflateRetry; those they decode are
+    // counted (pmc_ctx_guard_counts counts[4]: the lane route's, the wave-only route's chunk pass is uncounted)
+    bool retry_only, count_retried;
+
+    uint32_t ob;      // order kernels: blocks of 256
+    uint32_t lb;      // lane kernels: blocks of 64
+    // record kernel: the 1 KiB image instance when no member may decode to more (max_len: the largest
+    // capacity), else the 4 KiB one; rstride records per row.  rb: exactly the resident blocks -- a block owns
+    // its rows for the whole grid-stride loop, and blocks beyond residency would start only when the first
+    // ones have finished.  G, members per grab: the smallest power of two whose grabs fit the resident blocks
+    // once, so a small batch (a server's few hundred GETs) spreads one or a few members per wave instead of
+    // 64 on a few CUs with phase B's member-serial loop exposed.
+    bool out1k;
+    uint32_t rstride, G, rb, rec_max_out;
+    // verify kernel: members per wave as for the record kernel (a small batch takes one wave per member);
+    // blocks of 512
+    uint32_t VG, vb;
+    // chunk pass: blocks of 256 of its member kernels (scan, finish, count); blocks of 64 of the chunk kernel
+    // (the item count stays on the device: a grid of the resident waves strides over the items, and returns
+    // at once when there are none)
+    uint32_t mb, cb;
+    uint64_t hbm_waves;
+    uint32_t hbm_blocks; // of 4 waves
+    // scratch bytes: CRC-32 trailers, visit order (bins | member indices), record rows, the record kernel's
+    // list (count | members)
+    uint64_t crcx_bytes, order_bytes, recs_bytes, bigl_bytes;
+    // the chunk pass's rows in the context's idx buffer (byte offsets): cnt[n] u32 | fail[n] u32 | pre[n] u64 |
+    // bsum[nb] u64 (scan_u32's block sums, one per scan_block members) | total u64
+    struct Idx {
+        uint64_t cnt, fail, pre, bsum, total, bytes;
+    } idx;
+    // The LDS wave pass.  out_cap: output image capacity; the compressed input of a member whose output fits
+    // is at most gzip_bound(out) unless it is not a deflate member at all (lds_max_in).
+    // dict_out, the image: the dictionary, rounded to 16 bytes, in front of the plain members' out_cap bytes.
+    // A dictionary member starts at the image's first byte and needs dict_len + min(capacity, ISIZE) of it:
+    // that fits while its capacity is within max_len, which a device-resident caller need not keep -- max_len
+    // bounds the decompressed sizes, a slab passes its own.  The members this pass cannot hold go to a second
+    // launch sized for the longest dictionary member, dict_len + ISIZE = 16382; like the HBM variant it is
+    // always launched, the lengths being device-resident, unless this pass has that size already or a
+    // host-memory caller, who knows lengths and capacities, says that no member needs it.
+    uint64_t out_cap, lds_max_in;
+    uint32_t dict_out;
+    struct Second { // the second pass's InflateArgs fields of these names
+        uint64_t lds_max_out, lds_max_in;
+        uint32_t dict_out, first_img, first_in;
+    } second;
+};
+
+// the LDS wave pass's output image for a call with this max_len, and the staged input that goes with an image
+inline uint64_t inflate_out_cap(uint64_t max_len, uint64_t out_limit) {
+    return (std::min<uint64_t>(out_limit, std::max<uint64_t>(max_len, 1)) + 63) & ~(uint64_t)63;
+}
+inline uint64_t inflate_lds_in(uint64_t out_cap) { return gzip_bound(out_cap) + 64; }
+
+// A host-memory caller, who knows the lengths (max_in: the longest member), launches the wave kernels' HBM
+// variant (and the second dictionary pass) only when some member may exceed the LDS pass's image or input;
+// off the latency route they are always launched.
+inline bool inflate_need_hbm(bool latency, uint64_t max_len, uint64_t max_in, uint64_t out_limit) {
+    const uint64_t out_cap = inflate_out_cap(max_len, out_limit);
+    return !latency || max_len > out_cap || max_in > inflate_lds_in(out_cap);
+}
+
+inline InflatePlan plan_inflate(const InflateIn &in) {
+    InflatePlan P{};
+    const uint64_t n = in.n, max_len = in.max_len, cus = in.cus;
+    auto grid = [](uint64_t need, uint64_t cap) { return (uint32_t)std::min<uint64_t>(need, cap); };
+    // the smallest power of two G <= 64 with ceil(n / G) <= slots (64 if there is none)
+    auto group = [n](uint64_t slots) {
+        uint32_t G = 1;
+        while (G < 64 && (n + G - 1) / G > slots) G *= 2;
+        return G;
+    };
+    P.lane_route = !in.wave_only && !in.latency;
+    P.chunk_pass = !in.wave_only && max_len > kIdxChunk;
+    P.chunk_all = P.chunk_pass && in.latency;
+    P.order = P.lane_route && !in.no_order && n >= 4096;
+    P.rec = P.lane_route && !in.no_rec;
+    P.multi_pass = max_len > 16383;
+    P.verify = P.lane_route || P.chunk_pass;
+    P.hbm = in.need_hbm;
+    P.retry_only = P.lane_route || P.chunk_pass;
+    P.count_retried = P.lane_route;
+
+    P.ob = grid((n + 1023) / 1024, cus * 4);
+    P.lb = grid((n + 63) / 64, cus * 16);
+    P.out1k = max_len <= 1024;
+    P.rstride = (uint32_t)std::min<uint64_t>(in.rec_max, std::max<uint64_t>(64, (max_len + 63) & ~(uint64_t)63));
+    const uint64_t slots = cus * (P.out1k ? in.rec_per_cu_1k : in.rec_per_cu_4k);
+    P.G = group(slots);
+    P.rb = grid((n + P.G - 1) / P.G, slots);
+    P.rec_max_out = (uint32_t)(P.out1k ? 1024 : in.rec_out_max);
+    P.VG = group(cus * 32);
+    P.vb = grid((n + 8ull * P.VG - 1) / (8ull * P.VG), cus * 4);
+    P.mb = grid((n + 255) / 256, cus * 8);
+    P.cb = grid((n * kIdxMaxChunks + 63) / 64, cus * in.chunk_per_cu);
+    P.hbm_waves = std::min<uint64_t>(cus * 4, n);
+    P.hbm_blocks = (uint32_t)((P.hbm_waves + 3) / 4);
+
+    P.crcx_bytes = n * 4;
+    P.order_bytes = (uint64_t)kOrderBins * 4 + n * 4;
+    P.recs_bytes = (uint64_t)P.rb * 64 * P.rstride * 4 + 256;
+    P.bigl_bytes = n * 4 + 256;
+    const uint64_t nb = (n + in.scan_block - 1) / in.scan_block;
+    P.idx.cnt = 0;
+    P.idx.fail = 4 * n;
+    P.idx.pre = (8 * n + 7) & ~(uint64_t)7;
+    P.idx.bsum = P.idx.pre + 8 * n;
+    P.idx.total = P.idx.bsum + 8 * nb;
+    P.idx.bytes = P.idx.total + 8;
+
+    const uint32_t dD = in.dict_len;
+    P.out_cap = inflate_out_cap(max_len, in.out_limit);
+    P.lds_max_in = inflate_lds_in(P.out_cap);
+    P.dict_out = (uint32_t)(P.out_cap + ((dD + 15u) & ~15u));
+    const uint64_t dict_in = dD ? inflate_lds_in(kDictSpan - dD) : 0;
+    P.dict_second = dD && in.need_hbm && (P.dict_out < kDictSpan || P.lds_max_in < dict_in);
+    P.second.lds_max_out = (kDictSpan + 63) & ~63u;
+    P.second.dict_out = (uint32_t)P.second.lds_max_out;
+    P.second.lds_max_in = dict_in;
+    P.second.first_img = P.dict_out;
+    P.second.first_in = (uint32_t)P.lds_max_in;
+    return P;
 }
 
 } // namespace pmc

@@ -167,7 +167,7 @@ def gzip_bound(n: int) -> int:
 
 
 def gzip_bounds(lengths):
-    """pmc_gzip_bound of every length (numpy): the same closed form (csrc/pmc_kernels.hpp gzip_bound,
+    """pmc_gzip_bound of every length (numpy): the same closed form (csrc/pmc_plan.hpp gzip_bound,
     = oracle_gzip_bound; tests/test_abi.py checks them equal), without a C call per value."""
     import numpy as np
     n = np.asarray(lengths, dtype=np.uint64)

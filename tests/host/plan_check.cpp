@@ -7,6 +7,10 @@
 //   plan_check chunk <n> <budget> <cap>     split_chunk_of and split_value_bytes
 //   plan_check route                        one route per input line (the RouteIn fields in order, as
 //                                           integers), one JSON object per line
+//   plan_check inflate                      one decompress plan per input line (the InflateIn fields in order,
+//                                           as integers), one JSON object per line
+//   plan_check latency                      inflate_latency of each input line (its arguments in order): 0 or 1
+//   plan_check need_hbm                     inflate_need_hbm of each input line (its arguments in order): 0 or 1
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
@@ -62,16 +66,22 @@ static int layout(int argc, char **argv) {
     return 0;
 }
 
+// the integers of a line into v[0 .. want); false unless there are exactly `want`
+static bool ints(char *line, long long *v, int want) {
+    int got = 0;
+    for (char *p = line, *e; got <= want; got++, p = e) {
+        const long long x = strtoll(p, &e, 10);
+        if (e == p) break;
+        if (got < want) v[got] = x;
+    }
+    return got == want;
+}
+
 static int route() {
     char line[512];
     while (fgets(line, sizeof line, stdin)) {
-        long long v[17];
-        int got = 0;
-        for (char *p = line, *e; got < 17; got++, p = e) {
-            v[got] = strtoll(p, &e, 10);
-            if (e == p) break;
-        }
-        if (got != 16) return 2;
+        long long v[16];
+        if (!ints(line, v, 16)) return 2;
         const RouteIn in{(uint64_t)v[0], (uint64_t)v[1], (int)v[2], v[3] != 0, (uint32_t)v[4], (uint64_t)v[5],
                          v[6] != 0, v[7] != 0, v[8] != 0, v[9] != 0, (int)v[10], (uint64_t)v[11], (uint64_t)v[12],
                          (uint64_t)v[13], (uint64_t)v[14], (uint64_t)v[15]};
@@ -87,6 +97,49 @@ static int route() {
     return 0;
 }
 
+static int inflate() {
+    char line[512];
+    while (fgets(line, sizeof line, stdin)) {
+        long long v[16];
+        if (!ints(line, v, 16)) return 2;
+        const InflateIn in{(uint64_t)v[0], (uint64_t)v[1], (uint64_t)v[2], v[3] != 0, v[4] != 0, (uint32_t)v[5],
+                           v[6] != 0, v[7] != 0, v[8] != 0, (uint64_t)v[9], (uint64_t)v[10], (uint64_t)v[11],
+                           (uint64_t)v[12], (uint64_t)v[13], (uint64_t)v[14], (uint64_t)v[15]};
+        const InflatePlan p = plan_inflate(in);
+        printf("{\"lane_route\":%d,\"chunk_pass\":%d,\"chunk_all\":%d,\"order\":%d,\"rec\":%d,\"multi_pass\":%d,\"verify\":%d"
+               ",\"dict_second\":%d,\"hbm\":%d,\"retry_only\":%d,\"count_retried\":%d",
+               (int)p.lane_route, (int)p.chunk_pass, (int)p.chunk_all, (int)p.order, (int)p.rec, (int)p.multi_pass,
+               (int)p.verify, (int)p.dict_second, (int)p.hbm, (int)p.retry_only, (int)p.count_retried);
+        printf(",\"ob\":%u,\"lb\":%u,\"out1k\":%d,\"rstride\":%u,\"G\":%u,\"rb\":%u,\"rec_max_out\":%u,\"VG\":%u,\"vb\":%u"
+               ",\"mb\":%u,\"cb\":%u,\"hbm_waves\":%" PRIu64 ",\"hbm_blocks\":%u",
+               p.ob, p.lb, (int)p.out1k, p.rstride, p.G, p.rb, p.rec_max_out, p.VG, p.vb, p.mb, p.cb, p.hbm_waves, p.hbm_blocks);
+        printf(",\"crcx\":%" PRIu64 ",\"order_bytes\":%" PRIu64 ",\"recs\":%" PRIu64 ",\"bigl\":%" PRIu64, p.crcx_bytes,
+               p.order_bytes, p.recs_bytes, p.bigl_bytes);
+        printf(",\"idx\":{\"cnt\":%" PRIu64 ",\"fail\":%" PRIu64 ",\"pre\":%" PRIu64 ",\"bsum\":%" PRIu64 ",\"total\":%" PRIu64
+               ",\"bytes\":%" PRIu64 "}",
+               p.idx.cnt, p.idx.fail, p.idx.pre, p.idx.bsum, p.idx.total, p.idx.bytes);
+        printf(",\"out_cap\":%" PRIu64 ",\"lds_max_in\":%" PRIu64 ",\"dict_out\":%u", p.out_cap, p.lds_max_in, p.dict_out);
+        printf(",\"second\":{\"lds_max_out\":%" PRIu64 ",\"lds_max_in\":%" PRIu64 ",\"dict_out\":%u,\"first_img\":%u"
+               ",\"first_in\":%u}}\n",
+               p.second.lds_max_out, p.second.lds_max_in, p.second.dict_out, p.second.first_img, p.second.first_in);
+    }
+    return 0;
+}
+
+// inflate_latency (8 arguments) or inflate_need_hbm (4) of each input line
+static int predicate(int nargs) {
+    char line[512];
+    while (fgets(line, sizeof line, stdin)) {
+        long long v[8];
+        if (!ints(line, v, nargs)) return 2;
+        const bool b = nargs == 8 ? inflate_latency((uint64_t)v[0], (uint64_t)v[1], (uint64_t)v[2], (uint64_t)v[3], (uint64_t)v[4],
+                                                    (uint64_t)v[5], v[6] != 0, (uint64_t)v[7])
+                                  : inflate_need_hbm(v[0] != 0, (uint64_t)v[1], (uint64_t)v[2], (uint64_t)v[3]);
+        printf("%d\n", (int)b);
+    }
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc >= 2 && !strcmp(argv[1], "lv")) return lv(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "layout")) return layout(argc, argv);
@@ -96,6 +149,9 @@ int main(int argc, char **argv) {
         return 0;
     }
     if (argc == 2 && !strcmp(argv[1], "route")) return route();
-    fprintf(stderr, "usage: plan_check lv|layout|chunk|route ...\n");
+    if (argc == 2 && !strcmp(argv[1], "inflate")) return inflate();
+    if (argc == 2 && !strcmp(argv[1], "latency")) return predicate(8);
+    if (argc == 2 && !strcmp(argv[1], "need_hbm")) return predicate(4);
+    fprintf(stderr, "usage: plan_check lv|layout|chunk|route|inflate|latency|need_hbm ...\n");
     return 2;
 }

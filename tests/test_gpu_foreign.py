@@ -187,15 +187,16 @@ def test_general_decoder_on_small_members(ctx, golden):
 
 
 def test_record_kernel_1k_image(ctx, cases):
-    """More than 4,096 members with max_len <= 1024: inflate_rec_kernel<1024> (pmc_capi.hip:1129-1131,
-    out1k), the lane passes for what it marks too large for its rows, the wave kernels for what both decline."""
+    """More than 4,096 members with max_len <= 1024: inflate_rec_kernel<1024> (pmc_plan.hpp
+    InflatePlan::out1k), the lane passes for what it marks too large for its rows, the wave kernels for what both
+    decline."""
     part = [c for c in cases if c.cap <= 1024]
     assert max(c.cap for c in part) == 1024
     pipeline_route(ctx, part, 1024)
 
 
 def test_record_kernel_4k_image(ctx, cases):
-    """More than 4,096 members with max_len = 4096: inflate_rec_kernel<4096> (pmc_capi.hip:1129-1131)."""
+    """More than 4,096 members with max_len = 4096: inflate_rec_kernel<4096> (pmc_plan.hpp InflatePlan::out1k is off)."""
     part = [c for c in cases if c.cap <= 4096]
     assert max(c.cap for c in part) == 4096
     pipeline_route(ctx, part, 4096)
@@ -226,7 +227,7 @@ def test_lane_passes_with_the_multiblock_pass(ctx, cases):
 
 def test_host_calls(ctx, cases):
     """ctx.decompress_many: calls within the latency limits (<= 4,096 members of <= 48 KiB capacity and
-    <= 16 MiB of output, pmc_capi.hip latency_decompress) take the wave kernel over host memory, one call of
+    <= 16 MiB of output, pmc_plan.hpp inflate_latency) take the wave kernel over host memory, one call of
     more members takes the throughput pipeline -- both confirmed by the context's path counters."""
     import pmc_codec
 

@@ -1,8 +1,9 @@
-"""CPU: the compress call's planning arithmetic (csrc/pmc_plan.hpp), printed by tests/host/plan_check.cpp,
-equals a restatement of the formulas the host code had before the planner existed: the large-value rounds
-of both levels (counts, table and scratch offsets, filled tables, round splitting under a budget), the
-split pipeline's chunk-array layout, and the route (which path claims which lengths).  The restatement below
-is written from those formulas, not from pmc_plan.hpp."""
+"""CPU: the planning arithmetic of a compress and of a decompress call (csrc/pmc_plan.hpp), printed by
+tests/host/plan_check.cpp, equals a restatement of the formulas the host code had before the planner existed:
+the large-value rounds of both levels (counts, table and scratch offsets, filled tables, round splitting under
+a budget), the split pipeline's chunk-array layout, the compress route (which path claims which lengths), and
+the decompress plan (the wave-only route, which stages run, their grids, groups and scratch sizes).  The
+restatement below is written from those formulas, not from pmc_plan.hpp."""
 import itertools
 import json
 import os
@@ -414,3 +415,217 @@ def test_route_rows_pinned(plan_bin):
     assert b["passes"] == [[0, 14334, 14336, 1, 1], [14334, 16382, 16382, 1, 0]] and b["dict_len"] == 2048 and not b["lv"]
     assert c["passes"] == [[0, 16382, 16382, 0, 0], [16382, 30000, 30016, 0, 0]] and not c["lv"] and c["hbm_cut"] == 30000
     assert d["passes"] == [[0, 16382, 16382, 1, 0]] and d["lv"] and d["fast_all"] and d["hbm_cut"] == 16382
+
+
+# ---- the decompress plan, restated ------------------------------------------------------------------------
+# Written from the host code as it was before plan_inflate existed (decompress_batch_body, chunk_pass_decode,
+# latency_decompress and host_batch's need_hbm expression in pmc_capi.hip), branch by branch, not from
+# pmc_plan.hpp.
+IDX_CHUNK, IDX_MAX_CHUNKS = 32768, 16382
+REC_MAX, REC_OUT_MAX, SCAN_BLOCK, LDS_OUT_LIMIT = 2048, 4096, 1024, 48 * 1024
+# stand-ins for what the runtime answers on the device: resident blocks per CU of inflate_rec_kernel<1024>,
+# inflate_rec_kernel<4096> and inflate_chunk_kernel
+REC_PER_CU_1K, REC_PER_CU_4K, CHUNK_PER_CU = 8, 5, 20
+
+
+def gzip_bound(n):
+    return n + (n >> 3) + 6 * (n // 16383 + 1) + 32
+
+
+def want_inflate(n, max_len, cus, latency, need_hbm, dict_len, wave_only, no_order, no_rec, rec_1k, rec_4k, chunk_per_cu,
+                 rec_max, rec_out_max, scan_block, out_limit):
+    dD = dict_len
+    chunk_pass = not wave_only and max_len > IDX_CHUNK
+    retry_only = retried = order = rec = False
+    # "if (chunk_pass && latency)": the wave-only route's chunk pass, every member looked at
+    chunk_all = bool(chunk_pass and latency)
+    crcx = chunk_all
+    if chunk_all:
+        retry_only = True
+    # "if (!wave_only && !latency)": order, record kernel, lane passes, chunk pass, verify
+    lane = not wave_only and not latency
+    if lane:
+        crcx = True
+        order = not no_order and n >= 4096
+        rec = not no_rec
+        retry_only = retried = True
+    ob = min((n + 1023) // 1024, cus * 4)
+    lb = min((n + 63) // 64, cus * 16)
+    rstride = min(rec_max, max(64, (max_len + 63) & ~63))
+    out1k = max_len <= 1024
+    slots = cus * (rec_1k if out1k else rec_4k)
+    G = 1
+    while G < 64 and (n + G - 1) // G > slots:
+        G *= 2
+    rb = min((n + G - 1) // G, slots)
+    VG = 1
+    while VG < 64 and (n + VG - 1) // VG > cus * 32:
+        VG *= 2
+    vb = min((n + 8 * VG - 1) // (8 * VG), cus * 4)
+    # chunk_pass_decode
+    nb = (n + scan_block - 1) // scan_block
+    o_fail, o_pre = 4 * n, (8 * n + 7) & ~7
+    o_bsum = o_pre + 8 * n
+    mb = min((n + 255) // 256, cus * 8)
+    cb = min(cus * chunk_per_cu, (n * IDX_MAX_CHUNKS + 63) // 64)
+    # the wave kernels
+    out_cap = (min(out_limit, max(max_len, 1)) + 63) & ~63
+    lds_max_in = gzip_bound(out_cap) + 64
+    dict_out = out_cap + ((dD + 15) & ~15)
+    dict_in = gzip_bound(DICT_SPAN - dD) + 64 if dD else 0
+    dict_second = bool(dD and need_hbm and (dict_out < DICT_SPAN or lds_max_in < dict_in))
+    waves = min(cus * 4, n)
+    return {"lane_route": int(lane), "chunk_pass": int(chunk_pass), "chunk_all": int(chunk_all), "order": int(order),
+            "rec": int(rec), "multi_pass": int(max_len > 16383), "verify": int(crcx), "dict_second": int(dict_second),
+            "hbm": int(need_hbm), "retry_only": int(retry_only), "count_retried": int(retried),
+            "ob": ob, "lb": lb, "out1k": int(out1k), "rstride": rstride, "G": G, "rb": rb,
+            "rec_max_out": 1024 if out1k else rec_out_max, "VG": VG, "vb": vb, "mb": mb, "cb": cb, "hbm_waves": waves,
+            "hbm_blocks": (waves + 3) // 4,
+            "crcx": n * 4, "order_bytes": ORDER_BINS * 4 + n * 4, "recs": rb * 64 * rstride * 4 + 256, "bigl": n * 4 + 256,
+            "idx": {"cnt": 0, "fail": o_fail, "pre": o_pre, "bsum": o_bsum, "total": o_bsum + 8 * nb,
+                    "bytes": o_bsum + 8 * (nb + 1)},
+            "out_cap": out_cap, "lds_max_in": lds_max_in, "dict_out": dict_out,
+            "second": {"lds_max_out": (DICT_SPAN + 63) & ~63, "lds_max_in": dict_in, "dict_out": (DICT_SPAN + 63) & ~63,
+                       "first_img": dict_out, "first_in": lds_max_in}}
+
+
+def want_latency(n, max_len, out_bytes, cus, lat_batch, lat_max_len, device_call, out_limit):
+    lb, lm = 4 * lat_batch, lat_max_len
+    max_out = max(lm, out_limit) if lm else 0                                        # latency_max_out()
+    lat = n <= lb and max_len <= max_out and (max_len <= lm or out_bytes <= lb * lm)  # latency_decompress()
+    return bool(lat or (device_call and lat_batch != 0 and n <= 4 * cus))            # pmc_gzip_decompress_batch
+
+
+def want_need_hbm(latency, max_len, max_in, out_limit):
+    lim = (min(out_limit, max(max_len, 1)) + 63) & ~63  # inflate_lds_limit_out(max_len)
+    return bool(not latency or max_len > lim or max_in > gzip_bound(lim) + 64)
+
+
+def plan_lines(plan_bin, mode, rows):
+    text = "".join(" ".join(str(int(x)) for x in r) + "\n" for r in rows)
+    out = subprocess.run([plan_bin[0], mode], input=text, capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr
+    got = [json.loads(ln) for ln in out.stdout.splitlines()]
+    assert len(got) == len(rows)
+    return got
+
+
+def irow(n, max_len, cus=CUS, latency=False, need_hbm=True, dict_len=0, wave_only=False, no_order=False, no_rec=False):
+    return (n, max_len, cus, latency, need_hbm, dict_len, wave_only, no_order, no_rec, REC_PER_CU_1K, REC_PER_CU_4K,
+            CHUNK_PER_CU, REC_MAX, REC_OUT_MAX, SCAN_BLOCK, LDS_OUT_LIMIT)
+
+
+INFLATE_N = (1, 63, 64, 65, 4095, 4096, 4 * CUS, 4 * CUS + 1, 65536, 10_000_000)
+INFLATE_LENS = (1, 64, 1024, 1025, 4096, 4097, 16383, 16384, 32768, 32769, 49152, 49153, 65536, 1 << 20, U32MAX)
+
+
+def pow2_le_64(g):
+    return 1 <= g <= 64 and g & (g - 1) == 0
+
+
+def test_inflate_plan_matches_the_restated_formulas(plan_bin):
+    rows = [irow(n, max_len, cus, latency, need_hbm, dict_len, wave_only, no_order, no_rec)
+            for n, max_len, dict_len, latency, need_hbm, wave_only, no_order, no_rec, cus in itertools.product(
+                INFLATE_N, INFLATE_LENS, (0, 1, 2048, 8192), (False, True), (False, True), (False, True), (False, True),
+                (False, True), (8, 256))]
+    got = plan_lines(plan_bin, "inflate", rows)
+    for rw, g in zip(rows, got):
+        assert g == want_inflate(*rw), rw
+        n, max_len, cus, latency, need_hbm, dict_len, wave_only = rw[:7]
+        rec_per_cu = REC_PER_CU_1K if g["out1k"] else REC_PER_CU_4K
+        # every grid within [1, its residency cap]
+        for key, cap in (("ob", cus * 4), ("lb", cus * 16), ("rb", cus * rec_per_cu), ("vb", cus * 4), ("mb", cus * 8),
+                         ("cb", cus * CHUNK_PER_CU), ("hbm_blocks", cus), ("hbm_waves", cus * 4)):
+            assert 1 <= g[key] <= cap, (key, rw, g)
+        assert pow2_le_64(g["G"]) and pow2_le_64(g["VG"]), (rw, g)
+        assert -(-n // g["G"]) <= cus * rec_per_cu or g["G"] == 64, (rw, g)
+        assert -(-n // g["VG"]) <= cus * 32 or g["VG"] == 64, (rw, g)
+        assert g["rstride"] % 64 == 0 and 64 <= g["rstride"] <= REC_MAX, (rw, g)
+        # the idx rows: cnt u32[n] | fail u32[n] | pre u64[n] | bsum u64[nb] | total u64, none overlapping
+        ix, nb = g["idx"], -(-n // SCAN_BLOCK)
+        end = 0
+        for name, size in (("cnt", 4 * n), ("fail", 4 * n), ("pre", 8 * n), ("bsum", 8 * nb), ("total", 8)):
+            assert ix[name] >= end, (name, rw, g)
+            end = ix[name] + size
+        assert ix["pre"] % 8 == 0 and ix["bsum"] % 8 == 0 and ix["total"] % 8 == 0 and ix["bytes"] >= end, (rw, g)
+        assert bool(g["chunk_pass"]) == (not wave_only and max_len > 32768), (rw, g)
+        assert bool(g["retry_only"]) == bool(g["lane_route"] or g["chunk_pass"]), (rw, g)
+        assert not g["dict_second"] or (dict_len != 0 and need_hbm), (rw, g)
+        if dict_len:
+            assert g["second"]["dict_out"] >= DICT_SPAN and g["second"]["lds_max_out"] >= DICT_SPAN, (rw, g)
+            assert g["second"]["lds_max_in"] >= gzip_bound(DICT_SPAN - dict_len) + 64, (rw, g)
+        assert bool(g["multi_pass"]) == (max_len > 16383), (rw, g)
+
+
+def test_inflate_need_hbm_contract(plan_bin):
+    """Where inflate_need_hbm says no, the LDS pass of that call's plan holds every member: image >= max_len and
+    staged input >= max_in (else a host call would skip the HBM pass for a member the LDS pass cannot hold)."""
+    cases = []
+    for max_len in INFLATE_LENS:
+        out_cap = (min(LDS_OUT_LIMIT, max(max_len, 1)) + 63) & ~63
+        edge = gzip_bound(out_cap) + 64
+        cases += [(latency, max_len, max_in) for latency in (True, False) for max_in in (1, edge - 1, edge, edge + 1)]
+    got = plan_lines(plan_bin, "need_hbm", [(lat, ml, mi, LDS_OUT_LIMIT) for lat, ml, mi in cases])
+    plans = plan_lines(plan_bin, "inflate", [irow(400, ml, latency=lat, need_hbm=bool(nh)) for (lat, ml, mi), nh in zip(cases, got)])
+    said_no = 0
+    for (lat, max_len, max_in), nh, p in zip(cases, got, plans):
+        assert bool(nh) == want_need_hbm(lat, max_len, max_in, LDS_OUT_LIMIT), (lat, max_len, max_in)
+        if not nh:
+            said_no += 1
+            assert lat and p["out_cap"] >= max_len and p["lds_max_in"] >= max_in and not p["hbm"], (max_len, max_in, p)
+    assert said_no == 3 * sum(1 for ml in INFLATE_LENS if ml <= LDS_OUT_LIMIT)
+
+
+def test_inflate_latency_matches_the_restated_rule(plan_bin):
+    MiB16 = 16 << 20
+    rows = []
+    for cus, lat_batch, lat_max_len, device_call in itertools.product((8, 256, 2048), (1024, 0), (4096, 0), (False, True)):
+        for n in (1, 4096, 4097, 4 * cus, 4 * cus + 1):
+            for max_len in (1, 4096, 4097, 49152, 49153):
+                for out_bytes in (n * max_len, MiB16, MiB16 + 1):
+                    rows.append((n, max_len, out_bytes, cus, lat_batch, lat_max_len, device_call, LDS_OUT_LIMIT))
+    got = plan_lines(plan_bin, "latency", rows)
+    for rw, g in zip(rows, got):
+        assert bool(g) == want_latency(*rw), rw
+    lat = dict(zip(rows, got))
+    # the clauses by name: 4,096 members of 4 KiB; a 48 KiB member within 16 MiB in all; 4 members per CU on
+    # the device entry only; PMC_LATENCY_BATCH=0 and PMC_LATENCY_MAX_LEN=0 turn the route off
+    assert lat[(4096, 4096, 4096 * 4096, 256, 1024, 4096, False, LDS_OUT_LIMIT)] == 1
+    assert lat[(4097, 4096, 4097 * 4096, 256, 1024, 4096, False, LDS_OUT_LIMIT)] == 0
+    assert lat[(1, 49152, MiB16, 256, 1024, 4096, False, LDS_OUT_LIMIT)] == 1
+    assert lat[(1, 49152, MiB16 + 1, 256, 1024, 4096, False, LDS_OUT_LIMIT)] == 0
+    assert lat[(1, 49153, 49153, 256, 1024, 4096, False, LDS_OUT_LIMIT)] == 0
+    assert lat[(1, 49153, 49153, 256, 1024, 4096, True, LDS_OUT_LIMIT)] == 1
+    assert lat[(1024, 49153, 1024 * 49153, 256, 1024, 4096, True, LDS_OUT_LIMIT)] == 1
+    assert lat[(1025, 49153, 1025 * 49153, 256, 1024, 4096, True, LDS_OUT_LIMIT)] == 0
+    assert lat[(8192, 49153, 8192 * 49153, 2048, 1024, 4096, True, LDS_OUT_LIMIT)] == 1
+    assert lat[(8192, 49153, 8192 * 49153, 2048, 1024, 4096, False, LDS_OUT_LIMIT)] == 0
+    assert not any(g for rw, g in zip(rows, got) if rw[4] == 0)
+    assert not any(g for rw, g in zip(rows, got) if rw[5] == 0 and not (rw[6] and rw[0] <= 4 * rw[3]))
+
+
+def test_inflate_rows_pinned(plan_bin):
+    flat, host, wide, mid, dic = plan_lines(plan_bin, "inflate", [
+        irow(10_000_000, 1024),                             # the flagship batch: record kernel, 1 KiB instance
+        irow(400, 4096, latency=True, need_hbm=False),      # a host call of a server's GET batch
+        irow(1000, 1 << 20, latency=True),                  # at most 4 members per CU: wave kernels after the chunk pass
+        irow(40_000, 65536),                                # the pipeline with the multi-block pass and the chunk pass
+        irow(5000, 1024, dict_len=2048)])                   # a dictionary context: two LDS passes
+    stages = ("lane_route", "order", "rec", "multi_pass", "chunk_pass", "chunk_all", "verify", "dict_second", "hbm",
+              "retry_only", "count_retried")
+    on = lambda p: [s for s in stages if p[s]]
+    assert on(flat) == ["lane_route", "order", "rec", "verify", "hbm", "retry_only", "count_retried"]
+    assert (flat["ob"], flat["lb"], flat["out1k"], flat["rstride"], flat["G"], flat["rb"], flat["rec_max_out"]) == (
+        1024, 4096, 1, 1024, 64, 2048, 1024)
+    assert (flat["VG"], flat["vb"], flat["out_cap"], flat["lds_max_in"], flat["hbm_waves"], flat["hbm_blocks"]) == (
+        64, 1024, 1024, 1254, 1024, 256)
+    assert flat["recs"] == 2048 * 64 * 1024 * 4 + 256 and flat["crcx"] == 40_000_000
+    assert on(host) == [] and (host["out_cap"], host["lds_max_in"], host["dict_out"]) == (4096, 4710, 4096)
+    assert on(wide) == ["multi_pass", "chunk_pass", "chunk_all", "verify", "hbm", "retry_only"]
+    assert (wide["mb"], wide["cb"], wide["VG"], wide["vb"], wide["out_cap"], wide["hbm_waves"]) == (4, 5120, 1, 125, 49152, 1000)
+    assert wide["idx"] == {"cnt": 0, "fail": 4000, "pre": 8000, "bsum": 16000, "total": 16008, "bytes": 16016}
+    assert on(mid) == ["lane_route", "order", "rec", "multi_pass", "chunk_pass", "verify", "hbm", "retry_only", "count_retried"]
+    assert (mid["out1k"], mid["rstride"], mid["G"], mid["rb"], mid["rec_max_out"], mid["lb"]) == (0, 2048, 32, 1250, 4096, 625)
+    assert on(dic) == ["lane_route", "order", "rec", "verify", "dict_second", "hbm", "retry_only", "count_retried"]
+    assert (dic["out_cap"], dic["dict_out"], dic["lds_max_in"]) == (1024, 3072, 1254)
+    assert dic["second"] == {"lds_max_out": 16384, "lds_max_in": 16227, "dict_out": 16384, "first_img": 3072, "first_in": 1254}
