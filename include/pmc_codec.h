@@ -34,6 +34,8 @@ extern "C" {
 #define PMC_E_NO_DEVICE (-100)   /* no usable gfx950 device / HIP runtime error            */
 #define PMC_E_CAPACITY (-101)    /* output capacity too small; decompress: dst_len = needed  */
 #define PMC_E_ARG (-102)         /* invalid argument                                       */
+#define PMC_E_NO_INDEX (-103)    /* ranged read: this member cannot be served by the chunk path; a full
+                                    read gives the bytes or the verdict                      */
 
 /* One device + streams + scratch.  The host-memory calls (single value, *_batch_host,
  * *_batch_pinned) lock the context, so threads may share one (the drop-in shares the default
@@ -146,6 +148,55 @@ int pmc_ctx_set_index(pmc_ctx *ctx, int on);
 int pmc_ctx_get_index(pmc_ctx *ctx, int *on);
 int pmc_gzip_index_info(const void *member, size_t len, uint32_t *chunk_bytes, uint32_t *nchunks);
 int pmc_ctx_index_counts(pmc_ctx *ctx, uint64_t counts[2]);
+
+/* ---- ranged reads ------------------------------------------------------------------------------
+ * What the index is for: bytes [range_off, range_off + range_len) of a value, decoding only the chunks
+ * that hold them (csrc/pmc_inflate_range.hip).  Device-resident members only.
+ *
+ * pmc_gzip_decompress_range_batch: all arrays are device pointers; the call enqueues only -- no readback,
+ * no wait on the stream.  It is a decompress-direction call and uses the context's decompress scratch, so
+ * it is ordered with the other decompress calls of its context.  Per request i, in this order:
+ *   1. Index check.  The member must carry a valid index by the rules of pmc_gzip_index_info, with
+ *      log2 C <= 16 (the three chunk sizes the library can be built with; a scratch row is 64 KiB -- a full
+ *      read takes up to 2^24).  Otherwise rc[i] = PMC_E_NO_INDEX, dst_len[i] = 0, nothing is written.
+ *   2. Clamping.  With S = ISIZE: o = min(range_off, S), L = min(range_len, S - o) (Redis GETRANGE: a
+ *      range that reaches past the end is shortened, one that starts at or past the end is empty; no
+ *      32-bit wrap of range_off + range_len).
+ *   3. L == 0: rc[i] = PMC_OK, dst_len[i] = 0; nothing is decoded or written.
+ *   4. L > dst_cap[i]: rc[i] = PMC_E_CAPACITY, dst_len[i] = L; nothing is written.
+ *   5. Chunks o >> log2 C .. (o + L - 1) >> log2 C are decoded, and only those.  Each must pass exactly
+ *      the structural test of the full read's chunk pass: blocks the lane decoder takes (no stored
+ *      block), no distance before the chunk, exactly its bytes, then the empty stored block that ends on
+ *      the next index entry -- for the last chunk the final block, then the trailer that ends the member.
+ *      All pass: rc[i] = PMC_OK, dst_len[i] = L, dst[dst_off[i] .. + L) = value bytes [o, o + L).  Any
+ *      fails: rc[i] = PMC_E_NO_INDEX, dst_len[i] = 0.
+ * INTEGRITY: a ranged read vouches for the structure of the chunks it decoded.  It does not vouch for the
+ * member's CRC-32, which covers bytes it did not produce; a caller who needs the CRC does a full read.  A
+ * ranged read never gives a corrupt-stream verdict: it answers PMC_OK, PMC_E_NO_INDEX or PMC_E_CAPACITY,
+ * and after PMC_E_NO_INDEX the full read gives the bytes or the verdict.  The index stays advisory.
+ * WRITES: whatever the outcome, no byte outside [dst_off[i], dst_off[i] + min(L, dst_cap[i])) is written;
+ * on a non-OK rc that slot's content is unspecified.  dst_off may be unaligned.
+ * With PMC_INFLATE_WAVE=1 (the decompress fast paths off) every request is PMC_E_NO_INDEX.  n == 0 returns
+ * PMC_OK; a NULL context or (n > 0) a NULL array returns PMC_E_ARG without touching a device.
+ * Scratch: 16 bytes per request, and edge rows of 64 KiB + 16 that never exceed 2 GiB in all, whatever
+ * n and the ranges are (csrc/pmc_plan.hpp plan_range).  A call of n <= 16379 requests plans 2 n rows
+ * (1000 requests: 125 MiB); a larger one plans the whole grid's rows, 2 GiB, whether or not its ranges
+ * have edge chunks.  The context keeps the largest scratch a call has planned until pmc_ctx_destroy, as
+ * it keeps all its scratch: a caller who must not hold 2 GiB of HBM for ranged reads issues them in
+ * calls of at most 16379 requests.  pmc_store_get_range_batch passes its extents on in one call, so the
+ * same holds for its n and the store's context.
+ *
+ * pmc_ctx_range_counts synchronizes the device like pmc_ctx_index_counts: counts[0] = requests answered
+ * PMC_OK, counts[1] = requests answered PMC_E_NO_INDEX, counts[2] = chunks given to the decoder.
+ *
+ * (pmc_store_get_range_batch, below, is the call that always returns the range.)  Not provided: per-chunk
+ * CRCs (an index version 2), a host-memory entry point (it would ship whole members over PCIe), slab,
+ * group and server wrappers. */
+int pmc_gzip_decompress_range_batch(pmc_ctx *ctx, const uint8_t *src, const uint64_t *src_off,
+                                    const uint32_t *src_len, const uint32_t *range_off, const uint32_t *range_len,
+                                    uint32_t n, uint8_t *dst, const uint64_t *dst_off, const uint32_t *dst_cap,
+                                    uint32_t *dst_len, int32_t *rc, void *stream);
+int pmc_ctx_range_counts(pmc_ctx *ctx, uint64_t counts[3]);
 
 /* ---- preset dictionary ----------------------------------------------------------------------
  * A context holds at most one dictionary of 1 .. PMC_DICT_MAX bytes (host memory at the call, copied
@@ -351,6 +402,19 @@ int pmc_store_get_batch(pmc_store *s, const pmc_extent *ext, uint32_t n, int fra
  * custom and RESP requests side by side; responses at protocol.cpp:399-406 and :466-497). */
 int pmc_store_get_batch_frames(pmc_store *s, const pmc_extent *ext, uint32_t n, const uint8_t *frames,
                                const uint8_t **resp, uint32_t *resp_len, int32_t *rc);
+/* Bytes [o, o + L) of extent i's value, with o = min(range_off[i], raw_len) and L = min(range_len[i],
+ * raw_len - o) ("ranged reads", above), framed as pmc_store_get_batch frames a value (a RESP header carries
+ * L).  Synchronous, with the locks of pmc_store_get_batch; resp[i] points into the same pinned buffer.  It
+ * always returns the range, for every live extent: extents of an indexed member go through
+ * pmc_gzip_decompress_range_batch over the heap; those it answers PMC_E_NO_INDEX (small values, level-9
+ * members, chunks that hold stored blocks) and extents of raw_len <= 4096, which cannot carry an index, are
+ * decoded whole by pmc_gzip_decompress_batch into device scratch, CRC-checked, and only their slices come
+ * back; they get that full read's rc.  The whole reads run in rounds of at most 64 MiB of scratch
+ * (csrc/pmc_plan.hpp kRangeFallbackBudget; a larger extent gets a round of its own).  An empty or freed
+ * extent gives rc[i] = PMC_E_ARG. */
+int pmc_store_get_range_batch(pmc_store *s, const pmc_extent *ext, const uint32_t *range_off,
+                              const uint32_t *range_len, uint32_t n, int frame, const uint8_t **resp,
+                              uint32_t *resp_len, int32_t *rc);
 /* Copy extents' compressed bytes (gzip members) to host memory: member i at dst + dst_off[i]. */
 int pmc_store_read_members(pmc_store *s, const pmc_extent *ext, uint32_t n, uint8_t *dst,
                            const uint64_t *dst_off);

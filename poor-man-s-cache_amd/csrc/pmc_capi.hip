@@ -194,6 +194,10 @@ struct pmc_ctx {
     // inflate: resident blocks per CU of inflate_chunk_kernel and of the record kernel's 4 KiB [0] and 1 KiB [1]
     // instances (0: not asked yet; asked under the decompress lock)
     int chunk_per_cu = 0, rec_per_cu[2] = {0, 0};
+    // ranged reads (pmc_inflate_range.hip): the request rows and the edge rows (pmc_plan.hpp RangePlan); resident
+    // blocks per CU of inflate_range_kernel (0: not asked yet; asked under the decompress lock)
+    DevBuf rng;
+    int range_per_cu = 0;
     // preset dictionary (pmc_ctx_set_dictionary): its bytes on the device (zero padded to a multiple of 16),
     // length and id (CRC-32; 0 = none).  Written with host_mu and both dir_mu held, read under a dir_mu.
     DevBuf dict;
@@ -450,8 +454,9 @@ PMC_API int pmc_ctx_create(int device, pmc_ctx **out) {
     }
     // guard counters, and the lane-order self-test (lane_order_probe_kernel: 4 waves x 512 trials)
     uint32_t probe = 0;
-    // (bytes 32..47: the chunk pass's two u64 counters, pmc_ctx_index_counts)
-    if (c->guard.ensure(64) || hipMemsetAsync(c->guard.p, 0, 64, c->stream) != hipSuccess) {
+    // (bytes 32..47: the chunk pass's two u64 counters, pmc_ctx_index_counts; bytes 64..87: the ranged reads'
+    // three, pmc_ctx_range_counts)
+    if (c->guard.ensure(96) || hipMemsetAsync(c->guard.p, 0, 96, c->stream) != hipSuccess) {
         pmc_ctx_destroy(c);
         return PMC_E_NO_DEVICE;
     }
@@ -670,6 +675,7 @@ PMC_API void pmc_ctx_destroy(pmc_ctx *c) {
     c->recs.release();
     c->bigl.release();
     c->idx.release();
+    c->rng.release();
     c->dict.release();
     c->guard.release();
     c->rlist.release();
@@ -1399,6 +1405,84 @@ PMC_API int pmc_gzip_decompress_batch(pmc_ctx *ctx, const uint8_t *src, const ui
                               true);
     const int r2 = dir_leave(ctx, 1, st);
     return r ? r : r2;
+}
+
+// ---- ranged reads (pmc_inflate_range.hip; include/pmc_codec.h "ranged reads") ------------------------------
+// plan_range (pmc_plan.hpp) -> scan, prefix sum, one lane per covered chunk, finish.  Enqueue only, no readback.
+static int range_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t *src_off, const uint32_t *src_len,
+                            const uint32_t *range_off, const uint32_t *range_len, uint32_t n, uint8_t *dst,
+                            const uint64_t *dst_off, const uint32_t *dst_cap, uint32_t *dst_len, int32_t *rc,
+                            hipStream_t st) {
+    int r = PMC_OK;
+    if (!ctx->range_per_cu)
+        ctx->range_per_cu = occupancy_blocks((const void *)inflate_range_kernel, 64, kChunkLdsBytes);
+    const RangePlan P = plan_range(n, (uint64_t)ctx->cus, (uint64_t)ctx->range_per_cu, kIdxScanBlock);
+    if ((r = ctx->rng.ensure(P.bytes))) return r;
+    InflateArgs a{};
+    a.src = src;
+    a.src_off = src_off;
+    a.src_len = src_len;
+    a.dst = dst;
+    a.dst_off = dst_off;
+    a.dst_cap = dst_cap;
+    a.dst_len = dst_len;
+    a.rc = rc;
+    a.n = n;
+    uint8_t *p = (uint8_t *)ctx->rng.p;
+    uint64_t *pre = (uint64_t *)(p + P.idx.pre), *bsum = (uint64_t *)(p + P.idx.bsum);
+    RangeArgs R{};
+    R.range_off = range_off;
+    R.range_len = range_len;
+    R.cnt = (uint32_t *)(p + P.idx.cnt);
+    R.fail = (uint32_t *)(p + P.idx.fail);
+    R.pre = pre;
+    R.total = (uint64_t *)(p + P.idx.total);
+    R.counts = (uint64_t *)((uint8_t *)ctx->guard.p + 64);
+    R.rows = p + P.rows_off;
+    R.row_per_request = P.row_per_request ? 1 : 0;
+    R.off = inflate_env().wave_only ? 1 : 0;
+    klaunch(ctx, PMC_K_ORDER, st, [&] {
+        hipLaunchKernelGGL(inflate_range_scan_kernel, dim3(P.mb), dim3(256), 0, st, a, R);
+        r = scan_u32(R.cnt, nullptr, n, pre, bsum, st);
+    });
+    if (r) return r; // (scan_u32 has named the launch that failed)
+    klaunch(ctx, PMC_K_INFLATE_LANE, st, [&] {
+        hipLaunchKernelGGL(inflate_range_kernel, dim3(P.cb), dim3(64), kChunkLdsBytes, st, a, R);
+        hipLaunchKernelGGL(inflate_range_finish_kernel, dim3(P.mb), dim3(256), 0, st, a, R);
+    });
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_err("inflate_range_kernel", e);
+        return PMC_E_NO_DEVICE;
+    }
+    return PMC_OK;
+}
+
+PMC_API int pmc_gzip_decompress_range_batch(pmc_ctx *ctx, const uint8_t *src, const uint64_t *src_off,
+                                            const uint32_t *src_len, const uint32_t *range_off,
+                                            const uint32_t *range_len, uint32_t n, uint8_t *dst, const uint64_t *dst_off,
+                                            const uint32_t *dst_cap, uint32_t *dst_len, int32_t *rc, void *stream) {
+    if (!ctx || (n && (!src || !src_off || !src_len || !range_off || !range_len || !dst || !dst_off || !dst_cap ||
+                       !dst_len || !rc)))
+        return PMC_E_ARG;
+    if (n == 0) return PMC_OK;
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::recursive_mutex> dir_lock(ctx->dir_mu[1]);
+    int r = dir_enter(ctx, 1, st);
+    if (r) return r;
+    // (the direction event is recorded on every path, as pmc_gzip_decompress_batch records it: a scan may be
+    // enqueued on st when a later step fails)
+    r = range_batch_body(ctx, src, src_off, src_len, range_off, range_len, n, dst, dst_off, dst_cap, dst_len, rc, st);
+    const int r2 = dir_leave(ctx, 1, st);
+    return r ? r : r2;
+}
+
+PMC_API int pmc_ctx_range_counts(pmc_ctx *ctx, uint64_t counts[3]) {
+    if (!ctx || !counts) return PMC_E_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(counts, (uint8_t *)ctx->guard.p + 64, 24, hipMemcpyDeviceToHost));
+    return PMC_OK;
 }
 
 PMC_API int pmc_ctx_profile(pmc_ctx *ctx, int enable) {

@@ -1,0 +1,155 @@
+// pmc_inflate_range.hip -- ranged reads of indexed members (include/pmc_codec.h "ranged reads").
+//
+// An indexed member can be entered at every chunk, so a byte range of its value costs the chunks that hold it
+// and nothing else: one LANE per (request, covered chunk), decoding with the chunk pass's routine
+// (pmc_inflate_chunk.hip chunk_decode -- the same structural test, the same LDS layout).
+//   inflate_range_scan_kernel    one thread per request: the index check, the clamped range, the early verdicts
+//                                (an empty range, a capacity too small) and the number of covered chunks
+//   (exclusive prefix sum of the counts: scan_u32, pmc_capi.hip)
+//   inflate_range_kernel         one lane per covered chunk; a wave takes 64 consecutive items
+//   inflate_range_finish_kernel  one thread per request: rc, dst_len and the context's three counters
+// A chunk that lies wholly inside the range is decoded straight into its place in dst.  A chunk the range
+// covers only in part (at most two per request) is decoded whole into an edge row of the call's scratch -- its
+// matches may reach anywhere in the chunk -- and the lane then copies the wanted slice.  Nothing outside
+// [dst_off, dst_off + L) is written; no CRC is checked (the member's covers bytes this call did not produce),
+// and no verdict on the stream is given: a chunk that does not decode exactly as its index says declines the
+// request (PMC_E_NO_INDEX), and the caller's full read says why.
+#include <hip/hip_runtime.h>
+
+#include "pmc_device.hpp"
+#include "pmc_kernels.hpp"
+
+namespace pmc {
+
+__global__ void __launch_bounds__(256) inflate_range_scan_kernel(InflateArgs a, RangeArgs R) {
+    for (uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; v < a.n; v += (uint64_t)gridDim.x * blockDim.x) {
+        uint32_t lg, k, isz, hdr, items = 0, dl = 0;
+        int32_t rc = PMC_E_NO_INDEX;
+        if (!R.off && idx_parse(a.src + a.src_off[v], a.src_len[v], &lg, &k, &isz, &hdr) && lg <= kRangeLog2Max) {
+            const RangeOf r = range_of(isz, lg, R.range_off[v], R.range_len[v]);
+            if (r.L == 0) {
+                rc = PMC_OK;
+            } else if (r.L > a.dst_cap[v]) {
+                rc = PMC_E_CAPACITY;
+                dl = r.L;
+            } else { // (until the finish kernel: pending, with the length it will answer)
+                rc = kInflateRetry;
+                dl = r.L;
+                items = r.items;
+            }
+        }
+        R.cnt[v] = items;
+        R.fail[v] = 0;
+        a.rc[v] = rc;
+        a.dst_len[v] = dl;
+    }
+}
+
+// n bytes from byte s of the 16-byte aligned row (which has 16 readable bytes behind its chunk) to d
+// (global pointers, as the decoder's own stores to the row: see gload16)
+__device__ __forceinline__ void range_copy(uint8_t *dst, const uint8_t *src, uint32_t s, uint32_t n) {
+    PMC_GLB uint8_t *d = (PMC_GLB uint8_t *)dst;
+    PMC_GLB const uint8_t *row = (PMC_GLB const uint8_t *)src;
+    while (n && ((uintptr_t)d & 3)) {
+        *d++ = row[s++];
+        n--;
+    }
+    PMC_GLB const uint32_t *rw = (PMC_GLB const uint32_t *)row;
+    PMC_GLB uint32_t *dw = (PMC_GLB uint32_t *)d;
+    const uint32_t nw = n >> 2, k = s >> 2, sh = s & 3;
+#pragma unroll 4
+    for (uint32_t j = 0; j < nw; j++) dw[j] = __builtin_amdgcn_alignbyte(rw[k + j + 1], rw[k + j], sh);
+    for (uint32_t j = nw * 4; j < n; j++) d[j] = row[s + j];
+}
+
+__global__ void __launch_bounds__(64) inflate_range_kernel(InflateArgs a, RangeArgs R) {
+    typedef ChunkLayout LL;
+    extern __shared__ __attribute__((aligned(16))) uint16_t lcol[];
+    PMC_LDS uint16_t *col = to_lds<uint16_t>(lcol + threadIdx.x);
+    PMC_LDS uint32_t *ring = to_lds<uint32_t>((uint8_t *)lcol + LL::kRingOff) + threadIdx.x;
+    PMC_LDS uint8_t *bcol = to_lds<uint8_t>((uint8_t *)lcol + LL::kBColOff + threadIdx.x);
+    PMC_LDS uint32_t *winw = to_lds<uint32_t>((uint8_t *)lcol + LL::kWinOff) + threadIdx.x;
+    const uint64_t total = *R.total;
+    for (uint64_t ib = (uint64_t)blockIdx.x * 64; ib < total; ib += (uint64_t)gridDim.x * 64) {
+        const uint64_t it = ib + threadIdx.x;
+        uint32_t st = it < total ? 0u : 3u; // (chunk_decode: 0 an item, 3 none)
+        // the item's request: the last one whose prefix is <= it (requests of no items share their successor's)
+        uint64_t v = 0;
+        if (st == 0) {
+            uint64_t lo = 0, hi = a.n - 1;
+            while (lo < hi) {
+                const uint64_t mid = (lo + hi + 1) >> 1;
+                if (R.pre[mid] <= it) lo = mid;
+                else hi = mid - 1;
+            }
+            v = lo;
+        }
+        const uint8_t *m = st == 0 ? a.src + a.src_off[v] : a.src;
+        const uint32_t in_len = st == 0 ? a.src_len[v] : 0u;
+        uint32_t start = 0, next = 0, clen = 0, c0 = 0, lo = 0, hi = 0, o0 = 0;
+        bool lastc = true, whole = false;
+        uint8_t *row = R.rows, *slot = a.dst;
+        if (st == 0) {
+            const uint32_t lg = m[17];
+            const uint32_t isz = idx_u32(m + in_len - 4);
+            const uint32_t xlen = (uint32_t)m[10] | (uint32_t)m[11] << 8;
+            const RangeOf r = range_of(isz, lg, R.range_off[v], R.range_len[v]);
+            const uint32_t k = r.k0 + (uint32_t)(it - R.pre[v]);
+            const uint32_t K = (uint32_t)(((uint64_t)isz + (1u << lg) - 1) >> lg);
+            start = k == 0 ? 12 + xlen : idx_u32(m + kIdxHdrFixed + 4 * (k - 1));
+            lastc = k + 1 == K;
+            next = lastc ? in_len - 8 : idx_u32(m + kIdxHdrFixed + 4 * k);
+            c0 = k << lg; // (k < K: below ISIZE)
+            clen = isz - c0 < (1u << lg) ? isz - c0 : (1u << lg);
+            // the chunk's part of the range: value bytes [lo, hi), hi - lo >= 1
+            o0 = r.o;
+            lo = c0 > r.o ? c0 : r.o;
+            const uint64_t ce = (uint64_t)c0 + clen, re = (uint64_t)r.o + r.L;
+            hi = (uint32_t)(ce < re ? ce : re);
+            whole = lo == c0 && hi - lo == clen;
+            slot = a.dst + a.dst_off[v];
+            const uint64_t ri = R.row_per_request ? 2 * v + (k != r.k0 ? 1 : 0) : (uint64_t)blockIdx.x * 64 + threadIdx.x;
+            row = R.rows + ri * kRangeRowBytes;
+        }
+        st = chunk_decode<LL>(col, ring, bcol, winw, st, m, in_len, start, next, clen, lastc,
+                              whole ? slot + (c0 - o0) : row);
+        if (st == 2) R.fail[v] = 1;
+        // an edge chunk: the lane copies its own slice (its own stores, so no other lane's are waited for)
+        if (st == 8 && !whole) range_copy(slot + (lo - o0), row, lo - c0, hi - lo);
+    }
+}
+
+__global__ void __launch_bounds__(256) inflate_range_finish_kernel(InflateArgs a, RangeArgs R) {
+    // (every thread runs the same number of rounds: the ballots below are whole waves')
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, rounds = (a.n + stride - 1) / stride;
+    uint64_t served = 0, declined = 0, chunks = 0;
+    for (uint64_t q = 0; q < rounds; q++) {
+        const uint64_t v = q * stride + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        int32_t rc = 1;
+        if (v < a.n) {
+            const uint32_t c = R.cnt[v];
+            rc = a.rc[v];
+            if (c) {
+                chunks += c;
+                rc = R.fail[v] ? PMC_E_NO_INDEX : PMC_OK;
+                a.rc[v] = rc;
+                if (rc) a.dst_len[v] = 0;
+            }
+        }
+        served += rc == PMC_OK ? 1 : 0;
+        declined += rc == PMC_E_NO_INDEX ? 1 : 0;
+    }
+    // one atomic per wave and counter
+    for (int d = 32; d >= 1; d >>= 1) {
+        served += __shfl_xor((unsigned long long)served, d);
+        declined += __shfl_xor((unsigned long long)declined, d);
+        chunks += __shfl_xor((unsigned long long)chunks, d);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (served) atomicAdd((unsigned long long *)&R.counts[0], (unsigned long long)served);
+        if (declined) atomicAdd((unsigned long long *)&R.counts[1], (unsigned long long)declined);
+        if (chunks) atomicAdd((unsigned long long *)&R.counts[2], (unsigned long long)chunks);
+    }
+}
+
+} // namespace pmc

@@ -276,6 +276,22 @@ __global__ void inflate_chunk_scan_kernel(InflateArgs a, ChunkArgs X);
 __global__ void inflate_chunk_kernel(InflateArgs a, ChunkArgs X);
 __global__ void inflate_chunk_finish_kernel(InflateArgs a, ChunkArgs X);
 __global__ void inflate_chunk_count_kernel(InflateArgs a, ChunkArgs X);
+// ranged reads of indexed members (pmc_inflate_range.hip; include/pmc_codec.h "ranged reads"): the chunk
+// pass's rows per request, and the edge rows (pmc_plan.hpp RangePlan)
+struct RangeArgs {
+    const uint32_t *range_off, *range_len; // [n] the requests
+    uint32_t *cnt;         // [n] chunks the request covers, 0 = answered by the scan
+    const uint64_t *pre;   // [n] exclusive prefix sum of cnt: the request's first item
+    const uint64_t *total; // the number of items
+    uint32_t *fail;        // [n] some covered chunk did not decode as its index says
+    uint64_t *counts;      // the context's three counters (pmc_ctx_range_counts)
+    uint8_t *rows;         // edge rows of kRangeRowBytes
+    int32_t row_per_request; // rows 2 i, 2 i + 1 belong to request i; else row b * 64 + lane to the grid's lane
+    int32_t off;           // PMC_INFLATE_WAVE=1: the fast paths are off, every request is declined
+};
+__global__ void inflate_range_scan_kernel(InflateArgs a, RangeArgs R);
+__global__ void inflate_range_kernel(InflateArgs a, RangeArgs R);
+__global__ void inflate_range_finish_kernel(InflateArgs a, RangeArgs R);
 __global__ void arg_check_kernel(const uint32_t *src_len, uint64_t n, uint64_t max_len, int32_t *rc,
                                  uint32_t *dst_len);
 __global__ void lane_order_probe_kernel(uint32_t trials, uint32_t *violations);

@@ -205,6 +205,76 @@ PMC_HD inline bool idx_parse(P m, uint64_t len, uint32_t *log2c, uint32_t *K, ui
     return true;
 }
 
+// ---- ranged reads (include/pmc_codec.h "ranged reads"; pmc_inflate_range.hip) ----------------------------
+// the largest chunk a ranged read serves: the three sizes the library can be built with, and an edge row of
+// 64 KiB
+constexpr uint32_t kRangeLog2Max = 16;
+// an edge row: one chunk, and the 16 bytes LaneOut::get8's three-dword reads may reach past a position
+constexpr uint64_t kRangeRowBytes = (1ull << kRangeLog2Max) + 16;
+// all the edge rows of a call, whatever its n (allocated as far as a call's plan needs them, and then kept by
+// the context until pmc_ctx_destroy: its buffers grow and never shrink).  The budget cuts the range kernel's
+// grid, one row per lane, so it is a trade of HBM against decode rate: 2 GiB is 511 blocks, two thirds of the
+// resident lanes of a 256-CU device at three waves per CU; a call of n <= 16379 requests plans 2 n rows
+// (125 MiB for 1000) and is not cut
+constexpr uint64_t kRangeScratchBudget = 2048ull << 20;
+// the device scratch the store's fallback (whole reads of the extents the ranged call declined) uses per round;
+// an extent larger than this gets a round of its own
+constexpr uint64_t kRangeFallbackBudget = 64ull << 20;
+
+// The bytes [o, o + L) a request for [off, off + len) of a value of isize bytes gets (Redis GETRANGE: a range
+// that reaches past the end is shortened, one that starts at or past it is empty), and the chunks of 2^lg bytes
+// that hold them: k0 .. k0 + items - 1 (L 0: none).  No 32-bit wrap: off + len may exceed 2^32.
+struct RangeOf {
+    uint32_t o, L, k0, items;
+};
+PMC_HD inline RangeOf range_of(uint32_t isize, uint32_t lg, uint32_t off, uint32_t len) {
+    RangeOf r{};
+    r.o = off < isize ? off : isize;
+    r.L = len < isize - r.o ? len : isize - r.o;
+    if (r.L == 0) return r;
+    r.k0 = r.o >> lg;
+    r.items = (uint32_t)(((uint64_t)r.o + r.L - 1) >> lg) - r.k0 + 1;
+    return r;
+}
+
+// A ranged call over n requests.  Rows as the chunk pass's (InflatePlan::Idx), then the edge rows: a chunk that
+// the range covers only in part is decoded whole into a row, and its slice copied out.  A request has at most
+// two such chunks.  While 2 n rows fit the budget every request owns rows 2 i and 2 i + 1 and the range kernel
+// runs at the resident waves; a larger call gives every lane of the grid a row, reused across its grid-stride
+// loop, and cuts the grid to the rows the budget holds.  So the edge rows never exceed kRangeScratchBudget.
+struct RangePlan {
+    uint32_t mb, cb;   // blocks of 256 of the request kernels (scan, finish); blocks of 64 of the range kernel
+    bool row_per_request;
+    uint64_t rows;
+    struct Idx {
+        uint64_t cnt, fail, pre, bsum, total, bytes;
+    } idx;
+    uint64_t rows_off, edge_bytes, bytes; // the rows' offset (16-byte aligned), their bytes, the whole scratch
+};
+inline RangePlan plan_range(uint64_t n, uint64_t cus, uint64_t range_per_cu, uint64_t scan_block) {
+    RangePlan P{};
+    const uint64_t max_rows = kRangeScratchBudget / kRangeRowBytes;
+    const uint64_t resident = std::max<uint64_t>(1, cus * range_per_cu);
+    const uint64_t need = (std::min<uint64_t>(n, 1ull << 32) * kIdxMaxChunks + 63) / 64;
+    P.mb = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, cus * 8));
+    P.row_per_request = 2 * n <= max_rows;
+    uint64_t cb = std::max<uint64_t>(1, std::min(need, resident));
+    if (!P.row_per_request) cb = std::max<uint64_t>(1, std::min(cb, max_rows / 64));
+    P.cb = (uint32_t)cb;
+    P.rows = P.row_per_request ? 2 * n : cb * 64;
+    const uint64_t nb = (n + scan_block - 1) / scan_block;
+    P.idx.cnt = 0;
+    P.idx.fail = 4 * n;
+    P.idx.pre = (8 * n + 7) & ~(uint64_t)7;
+    P.idx.bsum = P.idx.pre + 8 * n;
+    P.idx.total = P.idx.bsum + 8 * nb;
+    P.idx.bytes = P.idx.total + 8;
+    P.rows_off = (P.idx.bytes + 15) & ~(uint64_t)15;
+    P.edge_bytes = P.rows * kRangeRowBytes;
+    P.bytes = P.rows_off + P.edge_bytes;
+    return P;
+}
+
 // ---- split pipeline chunk arrays (DeflateArgs cT .. cQ; pmc_deflate_split.hip) -------------------------
 constexpr uint32_t kSplitRows = 336;  // 286 lit/len + 30 dist + 19 bit-length (+1)
 constexpr uint32_t kMergeRows = 572;  // 2 heap entries per merge, <= 285 merges

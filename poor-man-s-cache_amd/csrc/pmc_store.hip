@@ -31,6 +31,8 @@ struct pmc_store {
     DevBuf pdev, gdev;    // device side of a put / a get: arrays + value bytes / response image
     HostBuf phost, ghost; // pinned host side of a put / the arrays of a get
     HostBuf hresp;        // pinned response image of the last get (resp[] points here)
+    DevBuf rdev;          // get_range: a fallback round's arrays + the whole values it decodes
+    HostBuf rhost;        // the arrays' pinned host side
 };
 
 namespace {
@@ -120,6 +122,8 @@ PMC_API void pmc_store_destroy(pmc_store *s) {
         s->phost.release();
         s->ghost.release();
         s->hresp.release();
+        s->rdev.release();
+        s->rhost.release();
         (void)hipStreamDestroy(s->gst);
     }
     delete s;
@@ -347,6 +351,178 @@ PMC_API int pmc_store_get_batch_frames(pmc_store *s, const pmc_extent *ext, uint
     for (uint32_t i = 0; i < n; i++)
         if (frames[i] > PMC_FRAME_RESP) return PMC_E_ARG;
     return store_get(s, ext, n, [frames](uint32_t i) { return (int)frames[i]; }, resp, resp_len, rc);
+}
+
+// Ranged get (include/pmc_codec.h pmc_store_get_range_batch): the ranged call over the heap for the extents
+// that may carry an index, then whole reads, in rounds of bounded scratch, of those it declined and of the
+// small ones; one D2H of the response image.
+PMC_API int pmc_store_get_range_batch(pmc_store *s, const pmc_extent *ext, const uint32_t *range_off,
+                                      const uint32_t *range_len, uint32_t n, int frame, const uint8_t **resp,
+                                      uint32_t *resp_len, int32_t *rc) {
+    if (!s || (n && (!ext || !range_off || !range_len || !resp || !resp_len || !rc)) || frame < PMC_FRAME_RAW ||
+        frame > PMC_FRAME_RESP)
+        return PMC_E_ARG;
+    if (n == 0) return PMC_OK;
+    StoreCall call(s, s->get_mu);
+    pmc_ctx *ctx = s->ctx;
+    auto digits = [](uint32_t v) {
+        uint32_t d = 1;
+        while (v >= 10) {
+            v /= 10;
+            d++;
+        }
+        return d;
+    };
+    const uint32_t tail = frame == PMC_FRAME_RESP ? 2 : frame == PMC_FRAME_CUSTOM ? 1 : 0;
+    // live extents: their clamped ranges and their places in the response image
+    std::vector<uint32_t> live, ranged, whole;
+    std::vector<uint64_t> pos(n, 0);
+    std::vector<uint32_t> ro(n, 0), rl(n, 0);
+    std::vector<uint8_t> hlen(n, 0);
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        resp[i] = nullptr;
+        resp_len[i] = 0;
+        if (!(ext[i].flags & 1) || ext[i].len == 0) {
+            rc[i] = PMC_E_ARG;
+            continue;
+        }
+        const RangeOf r = range_of(ext[i].raw_len, kRangeLog2Max, range_off[i], range_len[i]);
+        ro[i] = r.o;
+        rl[i] = r.L;
+        hlen[i] = (uint8_t)(frame == PMC_FRAME_RESP ? 1 + digits(r.L) + 2 : 0);
+        pos[i] = total;
+        total += hlen[i] + (uint64_t)r.L + tail;
+        rc[i] = PMC_OK;
+        live.push_back(i);
+        // (an empty range needs no device work; a value of <= 4096 bytes cannot carry an index)
+        if (r.L) (ext[i].raw_len > (1u << kIdxLog2Min) ? ranged : whole).push_back(i);
+    }
+    if (live.empty()) return PMC_OK;
+    // device staging: soff | doff (u64) | slen | roff | rlen | dcap | dlen | rc (u32) | response image
+    const uint32_t m = (uint32_t)ranged.size();
+    const uint64_t a8 = al256(m * 8ull), a4 = al256(m * 4ull), meta = a8 * 2 + a4 * 6;
+    int r = s->ghost.ensure(meta + 64);
+    if (!r) r = s->gdev.ensure(meta + total + 64);
+    if (!r) r = s->hresp.ensure(total + 64);
+    if (r) return r;
+    hipStream_t st = s->gst;
+    uint8_t *d_img = (uint8_t *)s->gdev.p + meta, *img = (uint8_t *)s->hresp.p;
+    if (m) {
+        uint8_t *hp = (uint8_t *)s->ghost.p, *dp = (uint8_t *)s->gdev.p;
+        uint64_t *h_soff = (uint64_t *)hp, *h_doff = (uint64_t *)(hp + a8);
+        uint32_t *h_slen = (uint32_t *)(hp + a8 * 2), *h_roff = (uint32_t *)(hp + a8 * 2 + a4);
+        uint32_t *h_rlen = (uint32_t *)(hp + a8 * 2 + a4 * 2), *h_dcap = (uint32_t *)(hp + a8 * 2 + a4 * 3);
+        uint32_t *h_dlen = (uint32_t *)(hp + a8 * 2 + a4 * 4);
+        int32_t *h_rc = (int32_t *)(hp + a8 * 2 + a4 * 5);
+        const uint64_t d_base = (uint64_t)(dp - hp);
+        auto dev = [&](void *h) { return (uint8_t *)h + d_base; };
+        for (uint32_t k = 0; k < m; k++) {
+            const uint32_t i = ranged[k];
+            h_soff[k] = ext[i].off;
+            h_slen[k] = ext[i].len;
+            h_roff[k] = ro[i];
+            h_rlen[k] = rl[i];
+            h_doff[k] = pos[i] + hlen[i];
+            h_dcap[k] = rl[i];
+        }
+        HIP_TRY(hipMemcpyAsync(dp, hp, meta, hipMemcpyHostToDevice, st));
+        r = pmc_gzip_decompress_range_batch(ctx, (const uint8_t *)s->heap.p, (uint64_t *)dev(h_soff), (uint32_t *)dev(h_slen),
+                                            (uint32_t *)dev(h_roff), (uint32_t *)dev(h_rlen), m, d_img,
+                                            (uint64_t *)dev(h_doff), (uint32_t *)dev(h_dcap), (uint32_t *)dev(h_dlen),
+                                            (int32_t *)dev(h_rc), st);
+        if (r) return r;
+        HIP_TRY(hipMemcpyAsync(h_dlen, dev(h_dlen), a4 * 2, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (uint32_t k = 0; k < m; k++) {
+            const uint32_t i = ranged[k];
+            if (h_rc[k] == PMC_E_NO_INDEX) whole.push_back(i);
+            else if (h_rc[k] != PMC_OK || h_dlen[k] != rl[i]) rc[i] = h_rc[k] != PMC_OK ? h_rc[k] : PMC_Z_DATA_ERROR;
+        }
+    }
+    // the whole reads: extents while their values fit the budget, and the first one always
+    for (size_t w0 = 0; w0 < whole.size();) {
+        size_t w1 = w0;
+        uint64_t bytes = 0, max_raw = 1;
+        while (w1 < whole.size()) {
+            const uint64_t need = ((uint64_t)ext[whole[w1]].raw_len + 15) & ~(uint64_t)15;
+            if (w1 > w0 && bytes + need > kRangeFallbackBudget) break;
+            bytes += need;
+            max_raw = std::max<uint64_t>(max_raw, ext[whole[w1]].raw_len);
+            w1++;
+        }
+        const uint32_t q = (uint32_t)(w1 - w0);
+        // round staging: soff | doff | cut (slice source) | poff (u64) | slen | dcap | dlen | rc | clen (u32) | values
+        const uint64_t b8 = al256(q * 8ull), b4 = al256(q * 4ull), rmeta = b8 * 4 + b4 * 5;
+        r = s->rhost.ensure(rmeta);
+        if (!r) r = s->rdev.ensure(rmeta + bytes + 64);
+        if (r) return r;
+        uint8_t *hp = (uint8_t *)s->rhost.p, *dp = (uint8_t *)s->rdev.p;
+        uint64_t *h_soff = (uint64_t *)hp, *h_doff = (uint64_t *)(hp + b8), *h_cut = (uint64_t *)(hp + b8 * 2);
+        uint64_t *h_poff = (uint64_t *)(hp + b8 * 3);
+        uint32_t *h_slen = (uint32_t *)(hp + b8 * 4), *h_dcap = (uint32_t *)(hp + b8 * 4 + b4);
+        uint32_t *h_dlen = (uint32_t *)(hp + b8 * 4 + b4 * 2);
+        int32_t *h_rc = (int32_t *)(hp + b8 * 4 + b4 * 3);
+        uint32_t *h_clen = (uint32_t *)(hp + b8 * 4 + b4 * 4);
+        const uint64_t d_base = (uint64_t)(dp - hp);
+        auto dev = [&](void *h) { return (uint8_t *)h + d_base; };
+        uint64_t at = 0;
+        for (uint32_t k = 0; k < q; k++) {
+            const uint32_t i = whole[w0 + k];
+            h_soff[k] = ext[i].off;
+            h_slen[k] = ext[i].len;
+            h_doff[k] = at;
+            h_dcap[k] = ext[i].raw_len;
+            h_cut[k] = at + ro[i];
+            h_clen[k] = rl[i];
+            h_poff[k] = pos[i] + hlen[i];
+            at += ((uint64_t)ext[i].raw_len + 15) & ~(uint64_t)15;
+        }
+        uint8_t *d_vals = dp + rmeta;
+        HIP_TRY(hipMemcpyAsync(dp, hp, rmeta, hipMemcpyHostToDevice, st));
+        r = pmc_gzip_decompress_batch(ctx, (const uint8_t *)s->heap.p, (uint64_t *)dev(h_soff), (uint32_t *)dev(h_slen), q,
+                                      d_vals, (uint64_t *)dev(h_doff), (uint32_t *)dev(h_dcap), (uint32_t *)dev(h_dlen),
+                                      (int32_t *)dev(h_rc), (uint32_t)max_raw, st);
+        if (r) return r;
+        // the slices of the values that decoded (rc 0) into their places in the image
+        hipLaunchKernelGGL(compact_kernel, dim3(std::min<uint32_t>((q + 3) / 4, 8192)), dim3(256), 0, st,
+                           (const uint8_t *)d_vals, (const uint64_t *)dev(h_cut), (const uint32_t *)dev(h_clen),
+                           (const int32_t *)dev(h_rc), (const uint64_t *)dev(h_poff), q, d_img);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h_dlen, dev(h_dlen), b4 * 2, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (uint32_t k = 0; k < q; k++) {
+            const uint32_t i = whole[w0 + k];
+            if (h_rc[k] != PMC_OK || h_dlen[k] != ext[i].raw_len) rc[i] = h_rc[k] != PMC_OK ? h_rc[k] : PMC_Z_DATA_ERROR;
+        }
+        w0 = w1;
+    }
+    if (total) {
+        HIP_TRY(hipMemcpyAsync(img, d_img, total, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    for (uint32_t i : live) {
+        if (rc[i] != PMC_OK) continue;
+        uint8_t *p = img + pos[i];
+        if (frame == PMC_FRAME_RESP) { // "$<len>\r\n" range bytes "\r\n"
+            const int nd = hlen[i] - 3;
+            p[0] = '$';
+            uint32_t v = rl[i];
+            for (int d = nd; d >= 1; d--) {
+                p[d] = (uint8_t)('0' + v % 10);
+                v /= 10;
+            }
+            p[nd + 1] = '\r';
+            p[nd + 2] = '\n';
+            p[hlen[i] + rl[i]] = '\r';
+            p[hlen[i] + rl[i] + 1] = '\n';
+        } else if (frame == PMC_FRAME_CUSTOM) {
+            p[rl[i]] = 0x1F;
+        }
+        resp[i] = p;
+        resp_len[i] = hlen[i] + rl[i] + tail;
+    }
+    return PMC_OK;
 }
 
 PMC_API int pmc_store_read_members(pmc_store *s, const pmc_extent *ext, uint32_t n, uint8_t *dst,

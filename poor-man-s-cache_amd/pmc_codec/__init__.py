@@ -28,6 +28,7 @@ Z_BUF_ERROR = -5
 E_NO_DEVICE = -100
 E_CAPACITY = -101
 E_ARG = -102
+E_NO_INDEX = -103  # ranged read: the member cannot be served by the chunk path (a full read answers)
 
 
 class CodecUnavailable(RuntimeError):
@@ -103,6 +104,9 @@ SIGNATURES = {
     "pmc_group_set_index": (_c.c_int, [_p, _c.c_int]),
     "pmc_gzip_index_info": (_c.c_int, [_c.c_char_p, _c.c_size_t, _c.POINTER(_u32), _c.POINTER(_u32)]),
     "pmc_ctx_index_counts": (_c.c_int, [_p, _c.POINTER(_u64)]),
+    "pmc_gzip_decompress_range_batch": (_c.c_int, [_p, _p, _p, _p, _p, _p, _u32, _p, _p, _p, _p, _p, _p]),
+    "pmc_ctx_range_counts": (_c.c_int, [_p, _c.POINTER(_u64)]),
+    "pmc_store_get_range_batch": (_c.c_int, [_p, _p, _p, _p, _u32, _c.c_int, _p, _p, _p]),
 }
 
 # compression levels (include/pmc_codec.h PMC_LEVEL_*)
@@ -247,6 +251,15 @@ class Context:
             raise CodecUnavailable(f"pmc_ctx_index_counts failed ({rc}): {last_error()}")
         return {"completed": c[0], "handed_over": c[1]}
 
+    def range_counts(self):
+        """{served, declined, chunks}: ranged requests answered OK / answered E_NO_INDEX, and the chunks given to
+        the decoder (include/pmc_codec.h pmc_ctx_range_counts)."""
+        c = (_u64 * 3)()
+        rc = lib().pmc_ctx_range_counts(self.handle, c)
+        if rc != 0:
+            raise CodecUnavailable(f"pmc_ctx_range_counts failed ({rc}): {last_error()}")
+        return {"served": c[0], "declined": c[1], "chunks": c[2]}
+
     def set_dictionary(self, dictionary):
         """Preset dictionary of 1 .. DICT_MAX bytes (None or b"" clears it): fast-level values of
         len(dictionary) + len <= 16382 bytes become dictionary members, which only a context holding the same
@@ -384,6 +397,16 @@ class Context:
         if r != 0:
             raise CodecUnavailable(f"pmc_gzip_decompress_batch = {r}: {last_error()}")
 
+    def decompress_range_device(self, src, src_off, src_len, range_off, range_len, dst, dst_off, dst_cap, dst_len, rc,
+                                stream=0):
+        """Bytes [range_off, range_off + range_len) of every member, decoding only the chunks that hold them
+        (include/pmc_codec.h "ranged reads").  Device tensors; enqueue only."""
+        r = lib().pmc_gzip_decompress_range_batch(self.handle, _ptr(src), _ptr(src_off), _ptr(src_len),
+                                                  _ptr(range_off), _ptr(range_len), _n(src_len), _ptr(dst),
+                                                  _ptr(dst_off), _ptr(dst_cap), _ptr(dst_len), _ptr(rc), stream)
+        if r != 0:
+            raise CodecUnavailable(f"pmc_gzip_decompress_range_batch = {r}: {last_error()}")
+
     # ---------------- pinned host batches, pipelined over copy streams --------------
     def compress_pinned(self, src, src_off, src_len, dst, dst_off, dst_cap, dst_len, rc, max_len, chunk=0):
         """All tensor arguments are pinned CPU tensors (torch pin_memory=True)."""
@@ -479,6 +502,26 @@ class Store:
         if r != 0:
             raise CodecUnavailable(f"pmc_store_get_batch = {r}: {last_error()}")
         return [(int(rc[i]), ctypes.string_at(resp[i], int(rlen[i])) if rc[i] == 0 else b"") for i in range(n)]
+
+    def get_range(self, ext, ranges, n=None, frame=FRAME_RAW):
+        """ranges: n pairs (offset, length), clamped to the value as Redis GETRANGE does -> list of
+        (rc, response bytes).  Decodes only the chunks a range needs where the member is indexed, the whole
+        value otherwise (pmc_store_get_range_batch)."""
+        import numpy as np
+        n = len(ext) if n is None else n
+        if n == 0:
+            return []
+        assert len(ranges) == n, (len(ranges), n)
+        roff = np.array([r[0] for r in ranges], dtype=np.uint32)
+        rlen = np.array([r[1] for r in ranges], dtype=np.uint32)
+        resp = (_p * n)()
+        plen = np.zeros(n, dtype=np.uint32)
+        rc = np.zeros(n, dtype=np.int32)
+        r = lib().pmc_store_get_range_batch(self.handle, ext, roff.ctypes.data, rlen.ctypes.data, n, frame, resp,
+                                            plen.ctypes.data, rc.ctypes.data)
+        if r != 0:
+            raise CodecUnavailable(f"pmc_store_get_range_batch = {r}: {last_error()}")
+        return [(int(rc[i]), ctypes.string_at(resp[i], int(plen[i])) if rc[i] == 0 else b"") for i in range(n)]
 
     def members(self, ext, n=None):
         import numpy as np

@@ -73,3 +73,23 @@ def decompress(ctx: Context, b: Batch, caps=None):
     ctx.decompress_device(b.data, b.off, b.len, dst, doff, dcap, dlen, rc, int(max(caps) if len(caps) else 0),
                           stream_handle())
     return Batch(dst, doff, dlen, b.n, int(max(caps) if len(caps) else 0)), rc
+
+
+def decompress_range(ctx: Context, b: Batch, offs, lens, align=1):
+    """Bytes [offs[i], offs[i] + lens[i]) of member i of the batch, clamped to its value as Redis GETRANGE does
+    (Context.decompress_range_device): slots of exactly the clamped lengths, `align` apart."""
+    dev = b.data.device
+    # the members' ISIZE trailers, gathered on the device: 4 n bytes come back, not the members
+    # (a member of under 4 bytes has none: its index is kept inside the buffer and its size taken as 0)
+    at = (b.off + b.len.to(torch.int64) - 4).unsqueeze(1) + torch.arange(4, device=dev)
+    tr = b.data[at.clamp_(0, max(b.data.numel() - 1, 0))].cpu().numpy().astype(np.int64)
+    ok = b.len.cpu().numpy() >= 4
+    isz = np.where(ok, tr[:, 0] | tr[:, 1] << 8 | tr[:, 2] << 16 | tr[:, 3] << 24, 0)
+    caps = [min(int(ln), int(s) - min(int(o), int(s))) for s, o, ln in zip(isz, offs, lens)]
+    dst, doff, dcap = slots_for(caps, dev, align)
+    roff = torch.from_numpy(np.asarray(offs, dtype=np.uint32).view(np.int32).copy()).to(dev)
+    rlen = torch.from_numpy(np.asarray(lens, dtype=np.uint32).view(np.int32).copy()).to(dev)
+    dlen = torch.zeros(b.n, dtype=torch.int32, device=dev)
+    rc = torch.zeros(b.n, dtype=torch.int32, device=dev)
+    ctx.decompress_range_device(b.data, b.off, b.len, roff, rlen, dst, doff, dcap, dlen, rc, stream_handle())
+    return Batch(dst, doff, dlen, b.n, int(max(caps) if len(caps) else 0)), rc
