@@ -46,8 +46,8 @@ typedef struct pmc_ctx pmc_ctx;
 
 /* Create a context on HIP device `device` (gfx950).  Returns PMC_OK or PMC_E_NO_DEVICE; PMC_E_ARG
  * (and a pmc_last_error text) when the environment variable PMC_LEVEL holds something else than
- * fast / 1 / fast-all / 2 / exact / 9 (see the levels below), PMC_INDEX something else than 1 / 0 (see "member
- * index"), or PMC_DICT names a file that is no dictionary (see "preset dictionary"). */
+ * fast / 1 / fast-all / 2 / exact / 9 (see the levels below), PMC_INDEX or PMC_INDEX_CRC something else than
+ * 1 / 0 (see "member index"), or PMC_DICT names a file that is no dictionary (see "preset dictionary"). */
 int pmc_ctx_create(int device, pmc_ctx **out);
 
 /* ---- compression level ------------------------------------------------------------------
@@ -143,11 +143,41 @@ int pmc_ctx_get_level(pmc_ctx *ctx, int *level);
  * offsets strictly increasing, the first behind the header, the last below len - 8), or PMC_E_ARG when
  * there is no valid one.  It does not check the stream.  Either output pointer may be NULL.
  * pmc_ctx_index_counts synchronizes the device like pmc_ctx_guard_counts: counts[0] = indexed members
- * the chunk pass completed, counts[1] = indexed members it took and then handed to the wave kernels. */
+ * the chunk pass completed, counts[1] = indexed members it took and then handed to the wave kernels.
+ *
+ * CHUNK CRCS.  A second switch, index_crc, off by default, acts only where the index switch acts and
+ * K <= 8190: the indexed member then also carries the CRC-32 of every chunk, in a second FEXTRA subfield
+ * directly behind the first.  The 'P' 'I' subfield is byte for byte as above; at byte p = 20 + 4 (K-1):
+ *
+ *   p       'P' 'C'  LEN u16 LE = 4 + 4 K
+ *   p + 4   version u8 = 1,  00 00 00
+ *   p + 8   K x u32 LE: zlib crc32() of value bytes [kC, min((k+1)C, len)), k = 0 .. K-1
+ *   p + 8 + 4 K   chunk 0's first block header        (XLEN = 8 K + 12; 16 bits hold K <= 8190)
+ *
+ * Tokens, blocks, separators and trailer are those of the plain indexed member, bit for bit; the offsets
+ * still count from the member's first byte, so each is 8 + 4 K larger.  With 8190 < K <= 16382 the value
+ * becomes the plain indexed member.  The member stays within pmc_gzip_bound(len): the subfield adds 8 + 4 K
+ * bytes, 4 per chunk and 8 once, and K >= 2 chunks mean len > (K-1) C, so the bound's len >> 3 term holds
+ * 4096 (K-1) >= 2048 K bytes beside the stored size of the value -- the 8 index and CRC bytes, the at most 5
+ * separator bytes and the extra block of a chunk, and the 8 bytes once, many times over.  A library that does
+ * not know the subfield reads the member unchanged: chunk 0 starts at 12 + XLEN for full and ranged reads alike
+ * (the rule XLEN >= LEN + 4 lets bytes follow the first subfield).  THE CRCS ARE ADVISORY as the index is:
+ * nothing in the subfield changes a full read's verdict or bytes, which keeps the member's CRC-32; they are
+ * what a ranged read (below) checks.  A member "carries chunk CRCs" when it carries a valid index and the
+ * 'P' 'C' subfield lies directly behind the 'P' 'I' one, wholly inside the FEXTRA field, with LEN = 4 + 4 K,
+ * version 1 and reserved bytes 0; any other member carries none.
+ * pmc_ctx_set_index_crc / pmc_ctx_get_index_crc, pmc_group_set_index_crc and the environment variable
+ * PMC_INDEX_CRC=1|0 follow the rules of their index counterparts above.  pmc_gzip_index_crc_info (host only)
+ * copies the K entries to crcs and sets *nchunks = K; PMC_E_ARG when the member carries none, PMC_E_CAPACITY
+ * (with *nchunks set) when cap < K.  crcs may be NULL when cap >= K is not needed (cap 0 asks for K alone);
+ * nchunks may be NULL. */
 int pmc_ctx_set_index(pmc_ctx *ctx, int on);
 int pmc_ctx_get_index(pmc_ctx *ctx, int *on);
 int pmc_gzip_index_info(const void *member, size_t len, uint32_t *chunk_bytes, uint32_t *nchunks);
 int pmc_ctx_index_counts(pmc_ctx *ctx, uint64_t counts[2]);
+int pmc_ctx_set_index_crc(pmc_ctx *ctx, int on);
+int pmc_ctx_get_index_crc(pmc_ctx *ctx, int *on);
+int pmc_gzip_index_crc_info(const void *member, size_t len, uint32_t *crcs, uint32_t cap, uint32_t *nchunks);
 
 /* ---- ranged reads ------------------------------------------------------------------------------
  * What the index is for: bytes [range_off, range_off + range_len) of a value, decoding only the chunks
@@ -159,6 +189,9 @@ int pmc_ctx_index_counts(pmc_ctx *ctx, uint64_t counts[2]);
  *   1. Index check.  The member must carry a valid index by the rules of pmc_gzip_index_info, with
  *      log2 C <= 16 (the three chunk sizes the library can be built with; a scratch row is 64 KiB -- a full
  *      read takes up to 2^24).  Otherwise rc[i] = PMC_E_NO_INDEX, dst_len[i] = 0, nothing is written.
+ *      With pmc_ctx_set_range_verify(ctx, 1) ("require") the member must also carry chunk CRCs ("member
+ *      index", above), or the answer is the same and nothing is decoded: steps 3 and 4 give their verdicts
+ *      only for members that pass this test.
  *   2. Clamping.  With S = ISIZE: o = min(range_off, S), L = min(range_len, S - o) (Redis GETRANGE: a
  *      range that reaches past the end is shortened, one that starts at or past the end is empty; no
  *      32-bit wrap of range_off + range_len).
@@ -168,10 +201,18 @@ int pmc_ctx_index_counts(pmc_ctx *ctx, uint64_t counts[2]);
  *      the structural test of the full read's chunk pass: blocks the lane decoder takes (no stored
  *      block), no distance before the chunk, exactly its bytes, then the empty stored block that ends on
  *      the next index entry -- for the last chunk the final block, then the trailer that ends the member.
+ *      Where the member carries chunk CRCs, the CRC-32 of every decoded chunk -- the whole chunk, also where
+ *      the range covers it in part -- must equal its entry.
  *      All pass: rc[i] = PMC_OK, dst_len[i] = L, dst[dst_off[i] .. + L) = value bytes [o, o + L).  Any
  *      fails: rc[i] = PMC_E_NO_INDEX, dst_len[i] = 0.
- * INTEGRITY: a ranged read vouches for the structure of the chunks it decoded.  It does not vouch for the
- * member's CRC-32, which covers bytes it did not produce; a caller who needs the CRC does a full read.  A
+ * INTEGRITY: a ranged read vouches for the structure of the chunks it decoded, and, where the member carries
+ * chunk CRCs, for their CRC-32s: the bytes it returns are then CRC-verified by the kernel that decoded them.
+ * Without chunk CRCs it vouches for the structure alone -- not for the member's CRC-32, which covers bytes it
+ * did not produce -- and a caller who needs more does a full read, or sets pmc_ctx_set_range_verify(ctx, 1):
+ * the call then declines every member without chunk CRCs, so that every PMC_OK is a verified one (0, the
+ * default: check where present; anything else, or a NULL context, gives PMC_E_ARG and touches no device; it
+ * takes effect for the calls issued after it returns).  A damaged CRC entry declines the requests that touch
+ * its chunk and no others; the full read does not look at it.  A
  * ranged read never gives a corrupt-stream verdict: it answers PMC_OK, PMC_E_NO_INDEX or PMC_E_CAPACITY,
  * and after PMC_E_NO_INDEX the full read gives the bytes or the verdict.  The index stays advisory.
  * WRITES: whatever the outcome, no byte outside [dst_off[i], dst_off[i] + min(L, dst_cap[i])) is written;
@@ -188,15 +229,21 @@ int pmc_ctx_index_counts(pmc_ctx *ctx, uint64_t counts[2]);
  *
  * pmc_ctx_range_counts synchronizes the device like pmc_ctx_index_counts: counts[0] = requests answered
  * PMC_OK, counts[1] = requests answered PMC_E_NO_INDEX, counts[2] = chunks given to the decoder.
+ * pmc_ctx_range_verify_counts synchronizes the same way: counts[0] = chunks whose CRC was checked and matched,
+ * counts[1] = chunks whose CRC did not match.
  *
- * (pmc_store_get_range_batch, below, is the call that always returns the range.)  Not provided: per-chunk
- * CRCs (an index version 2), a host-memory entry point (it would ship whole members over PCIe), slab,
- * group and server wrappers. */
+ * (pmc_store_get_range_batch, below, is the call that always returns the range: what the ranged call declines
+ * it reads whole, CRC-checked, so on a context in "require" mode every byte it returns has been verified one
+ * way or the other.)  Not provided: chunk CRCs in the full read (it keeps the member's), a host-memory entry
+ * point (it would ship whole members over PCIe), slab, group and server wrappers. */
 int pmc_gzip_decompress_range_batch(pmc_ctx *ctx, const uint8_t *src, const uint64_t *src_off,
                                     const uint32_t *src_len, const uint32_t *range_off, const uint32_t *range_len,
                                     uint32_t n, uint8_t *dst, const uint64_t *dst_off, const uint32_t *dst_cap,
                                     uint32_t *dst_len, int32_t *rc, void *stream);
 int pmc_ctx_range_counts(pmc_ctx *ctx, uint64_t counts[3]);
+int pmc_ctx_set_range_verify(pmc_ctx *ctx, int mode);
+int pmc_ctx_get_range_verify(pmc_ctx *ctx, int *mode);
+int pmc_ctx_range_verify_counts(pmc_ctx *ctx, uint64_t counts[2]);
 
 /* ---- preset dictionary ----------------------------------------------------------------------
  * A context holds at most one dictionary of 1 .. PMC_DICT_MAX bytes (host memory at the call, copied
@@ -422,6 +469,9 @@ int pmc_store_read_members(pmc_store *s, const pmc_extent *ext, uint32_t n, uint
 int pmc_store_free(pmc_store *s, pmc_extent *ext, uint32_t n);
 /* used: bytes held by live extents; reserved: heap bytes handed out so far; heap: heap size. */
 int pmc_store_stats(pmc_store *s, uint64_t *used, uint64_t *reserved, uint64_t *heap);
+/* The heap's base (a device pointer; NULL for a NULL store): extent i's member lies at base + ext[i].off, as
+ * pmc_slab_data() + s * stride does for a slab.  For diagnostics and tests -- the store owns the bytes. */
+uint8_t *pmc_store_data(pmc_store *s);
 
 /* ---- fixed-slot device slab (device-resident callers) ---------------------
  * For callers whose keys, values and bookkeeping already live on the device (bench.py --mix,
@@ -461,6 +511,8 @@ int pmc_group_size(pmc_group *g);
 int pmc_group_set_level(pmc_group *g, int level);
 /* pmc_ctx_set_index on every member context (all or none; see "member index"). */
 int pmc_group_set_index(pmc_group *g, int on);
+/* pmc_ctx_set_index_crc on every member context (all or none; see "member index", chunk CRCs). */
+int pmc_group_set_index_crc(pmc_group *g, int on);
 /* pmc_ctx_set_dictionary on every member context (all or none; see "preset dictionary"). */
 int pmc_group_set_dictionary(pmc_group *g, const void *dict, size_t len);
 /* member[i] = (key_hash[i] % num_shards) % pmc_group_size(g) */

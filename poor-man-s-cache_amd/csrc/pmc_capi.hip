@@ -190,6 +190,9 @@ struct pmc_ctx {
     std::atomic<int> level{PMC_LEVEL_EXACT};
     // the index switch of the calls issued from now on (pmc_ctx_set_index; include/pmc_codec.h "member index")
     std::atomic<int> index{0};
+    // the chunk-CRC switch of the compress calls (pmc_ctx_set_index_crc) and the verification mode of the ranged
+    // reads (pmc_ctx_set_range_verify: 0 check where present, 1 require) issued from now on
+    std::atomic<int> index_crc{0}, range_verify{0};
     DevBuf idx;                  // inflate: the chunk pass's rows (counts | fail | prefix | block sums)
     // inflate: resident blocks per CU of inflate_chunk_kernel and of the record kernel's 4 KiB [0] and 1 KiB [1]
     // instances (0: not asked yet; asked under the decompress lock)
@@ -378,6 +381,13 @@ static int env_index() {
     return !strcmp(e, "1") ? 1 : !strcmp(e, "0") ? 0 : -1;
 }
 
+// PMC_INDEX_CRC: the same for the chunk-CRC switch.
+static int env_index_crc() {
+    const char *e = getenv("PMC_INDEX_CRC");
+    if (!e) return 0;
+    return !strcmp(e, "1") ? 1 : !strcmp(e, "0") ? 0 : -1;
+}
+
 static int env_dictionary(std::vector<uint8_t> &bytes);
 static uint32_t host_crc32(const uint8_t *p, size_t n);
 static int set_dictionary_locked(pmc_ctx *ctx, const void *dict, size_t len, uint32_t id);
@@ -392,6 +402,11 @@ PMC_API int pmc_ctx_create(int device, pmc_ctx **out) {
     const int idx = env_index();
     if (idx < 0) {
         g_err = std::string("PMC_INDEX=") + getenv("PMC_INDEX") + ": expected 1 or 0";
+        return PMC_E_ARG;
+    }
+    const int idx_crc = env_index_crc();
+    if (idx_crc < 0) {
+        g_err = std::string("PMC_INDEX_CRC=") + getenv("PMC_INDEX_CRC") + ": expected 1 or 0";
         return PMC_E_ARG;
     }
     std::vector<uint8_t> env_dict; // PMC_DICT: checked before any device is touched, as PMC_LEVEL
@@ -446,6 +461,7 @@ PMC_API int pmc_ctx_create(int device, pmc_ctx **out) {
     c->device = device;
     c->cus = prop.multiProcessorCount;
     c->index = idx;
+    c->index_crc = idx_crc;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&c->dir_ev[0], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->dir_ev[1], hipEventDisableTiming) != hipSuccess) {
@@ -455,8 +471,9 @@ PMC_API int pmc_ctx_create(int device, pmc_ctx **out) {
     // guard counters, and the lane-order self-test (lane_order_probe_kernel: 4 waves x 512 trials)
     uint32_t probe = 0;
     // (bytes 32..47: the chunk pass's two u64 counters, pmc_ctx_index_counts; bytes 64..87: the ranged reads'
-    // three, pmc_ctx_range_counts)
-    if (c->guard.ensure(96) || hipMemsetAsync(c->guard.p, 0, 96, c->stream) != hipSuccess) {
+    // three, pmc_ctx_range_counts; bytes 96..111: their two verification counters, pmc_ctx_range_verify_counts;
+    // bytes 112..115: RangeArgs::ncrc of the ranged call in flight)
+    if (c->guard.ensure(128) || hipMemsetAsync(c->guard.p, 0, 128, c->stream) != hipSuccess) {
         pmc_ctx_destroy(c);
         return PMC_E_NO_DEVICE;
     }
@@ -516,6 +533,30 @@ PMC_API int pmc_gzip_index_info(const void *member, size_t len, uint32_t *chunk_
     if (!member || !idx_parse((const uint8_t *)member, len, &lg, &K, &isz, &hdr)) return PMC_E_ARG;
     if (chunk_bytes) *chunk_bytes = 1u << lg;
     if (nchunks) *nchunks = K;
+    return PMC_OK;
+}
+
+// chunk CRCs (include/pmc_codec.h "member index", chunk CRCs)
+PMC_API int pmc_ctx_set_index_crc(pmc_ctx *ctx, int on) {
+    if (!ctx || (on != 0 && on != 1)) return PMC_E_ARG;
+    ctx->index_crc = on;
+    return PMC_OK;
+}
+
+PMC_API int pmc_ctx_get_index_crc(pmc_ctx *ctx, int *on) {
+    if (!ctx || !on) return PMC_E_ARG;
+    *on = ctx->index_crc;
+    return PMC_OK;
+}
+
+PMC_API int pmc_gzip_index_crc_info(const void *member, size_t len, uint32_t *crcs, uint32_t cap, uint32_t *nchunks) {
+    uint32_t K = 0, at = 0;
+    if (!member || !idx_crc_parse((const uint8_t *)member, len, &K, &at)) return PMC_E_ARG;
+    if (nchunks) *nchunks = K;
+    if (cap < K) return PMC_E_CAPACITY;
+    const uint8_t *e = (const uint8_t *)member + at;
+    for (uint32_t k = 0; crcs && k < K; k++, e += 4)
+        crcs[k] = (uint32_t)e[0] | (uint32_t)e[1] << 8 | (uint32_t)e[2] << 16 | (uint32_t)e[3] << 24;
     return PMC_OK;
 }
 
@@ -798,6 +839,7 @@ static int large_values(pmc_ctx *ctx, const DeflateArgs &a, uint64_t lo, uint64_
     const uint64_t budget = 24ull << 30;
     // (the index switch acts on the segmented fast members only; read once per call)
     const uint32_t idx_chunk = fast && ctx->index ? kIdxChunk : 0u;
+    const uint32_t idx_crc = idx_chunk && ctx->index_crc ? 1u : 0u;
     const uint64_t fwb = fast ? lv_fast_wave_bytes() : 0;
     const Launch Lp = fast ? plan_lds(ctx, (const void *)lv_fast_parse_kernel, fwb, 1ull << 40, 0) : Launch{};
     for (size_t v0 = 0; v0 < vals.size();) {
@@ -839,6 +881,7 @@ static int large_values(pmc_ctx *ctx, const DeflateArgs &a, uint64_t lo, uint64_
         // the small fast members
         L.xfl = fast ? 4 : 2;
         L.idx_chunk = idx_chunk;
+        L.idx_crc = idx_crc;
         if (fast) {
             HIP_TRY(hipMemsetAsync(L.fail, 0, 4ull * R.nv, st));
             DeflateArgs p = a;
@@ -1415,7 +1458,7 @@ static int range_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t *sr
                             hipStream_t st) {
     int r = PMC_OK;
     if (!ctx->range_per_cu)
-        ctx->range_per_cu = occupancy_blocks((const void *)inflate_range_kernel, 64, kChunkLdsBytes);
+        ctx->range_per_cu = occupancy_blocks((const void *)inflate_range_kernel<false>, 64, kChunkLdsBytes);
     const RangePlan P = plan_range(n, (uint64_t)ctx->cus, (uint64_t)ctx->range_per_cu, kIdxScanBlock);
     if ((r = ctx->rng.ensure(P.bytes))) return r;
     InflateArgs a{};
@@ -1438,6 +1481,9 @@ static int range_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t *sr
     R.pre = pre;
     R.total = (uint64_t *)(p + P.idx.total);
     R.counts = (uint64_t *)((uint8_t *)ctx->guard.p + 64);
+    R.vcounts = (uint64_t *)((uint8_t *)ctx->guard.p + 96);
+    R.require = ctx->range_verify ? 1 : 0;
+    R.ncrc = (uint32_t *)((uint8_t *)ctx->guard.p + 112);
     R.rows = p + P.rows_off;
     R.row_per_request = P.row_per_request ? 1 : 0;
     R.off = inflate_env().wave_only ? 1 : 0;
@@ -1447,7 +1493,8 @@ static int range_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t *sr
     });
     if (r) return r; // (scan_u32 has named the launch that failed)
     klaunch(ctx, PMC_K_INFLATE_LANE, st, [&] {
-        hipLaunchKernelGGL(inflate_range_kernel, dim3(P.cb), dim3(64), kChunkLdsBytes, st, a, R);
+        hipLaunchKernelGGL(inflate_range_kernel<false>, dim3(P.cb), dim3(64), kChunkLdsBytes, st, a, R);
+        hipLaunchKernelGGL(inflate_range_kernel<true>, dim3(P.cb), dim3(64), kRangeLdsBytes, st, a, R);
         hipLaunchKernelGGL(inflate_range_finish_kernel, dim3(P.mb), dim3(256), 0, st, a, R);
     });
     hipError_t e = hipGetLastError();
@@ -1482,6 +1529,26 @@ PMC_API int pmc_ctx_range_counts(pmc_ctx *ctx, uint64_t counts[3]) {
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(counts, (uint8_t *)ctx->guard.p + 64, 24, hipMemcpyDeviceToHost));
+    return PMC_OK;
+}
+
+PMC_API int pmc_ctx_set_range_verify(pmc_ctx *ctx, int mode) {
+    if (!ctx || (mode != 0 && mode != 1)) return PMC_E_ARG;
+    ctx->range_verify = mode;
+    return PMC_OK;
+}
+
+PMC_API int pmc_ctx_get_range_verify(pmc_ctx *ctx, int *mode) {
+    if (!ctx || !mode) return PMC_E_ARG;
+    *mode = ctx->range_verify;
+    return PMC_OK;
+}
+
+PMC_API int pmc_ctx_range_verify_counts(pmc_ctx *ctx, uint64_t counts[2]) {
+    if (!ctx || !counts) return PMC_E_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(counts, (uint8_t *)ctx->guard.p + 96, 16, hipMemcpyDeviceToHost));
     return PMC_OK;
 }
 

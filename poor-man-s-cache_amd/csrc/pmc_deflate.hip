@@ -393,22 +393,39 @@ struct DeflateWave {
                           const LargeArgs &L, uint32_t ov, PMC_LDS uint32_t *hist) {
         const int l = lane_id();
         const Tables &T = c_tables;
-        const uint32_t crc = wave_crc32(src, (uint32_t)len, crc_tab);
+        // an indexed value (include/pmc_codec.h "member index"): FLG = FEXTRA, and the 'P' 'I' subfield whose
+        // offsets are filled in as the chunks are reached
+        const IdxPlan ix = idx_plan(len, L.idx_chunk, L.idx_crc != 0);
+        uint32_t crc = 0;
+        if (!ix.crcs) crc = wave_crc32(src, (uint32_t)len, crc_tab);
         for (uint64_t k = l; k < out_words; k += 64) outw[k] = 0;
         for (int k = l; k < 320; k += 64) hist[k] = 0;
         sync();
-        // an indexed value (include/pmc_codec.h "member index"): FLG = FEXTRA, and the 'P' 'I' subfield whose
-        // offsets are filled in as the chunks are reached
-        const IdxPlan ix = idx_plan(len, L.idx_chunk);
         if (l < 10) {
             const uint8_t hdr[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 2, 3};
             outb[l] = l == 8 ? (uint8_t)L.xfl : l == 3 && ix.indexed ? (uint8_t)4 : hdr[l];
         } else if (l < 20 && ix.indexed) {
             // bytes 10..17: XLEN | 'P' 'I' | LEN | version 1 | log2 C, then 00 00 (shifted out of one word: a local
             // array indexed by the lane would live in scratch memory)
-            const uint64_t xlen = ix.hdr - 12, sl = xlen - 4, lg = 31 - __builtin_clz(L.idx_chunk);
+            const uint64_t xlen = ix.hdr - 12, sl = 4 * (uint64_t)ix.K, lg = 31 - __builtin_clz(L.idx_chunk);
             const uint64_t ext = xlen | (uint64_t)'P' << 16 | (uint64_t)'I' << 24 | sl << 32 | 1ull << 48 | lg << 56;
             outb[l] = l < 18 ? (uint8_t)(ext >> (8 * (l - 10))) : (uint8_t)0;
+        } else if (l < 28 && ix.crcs) {
+            // the chunk CRCs' subfield behind the offsets: 'P' 'C' | LEN = 4 + 4 K | version 1 | 00 00 00
+            const uint64_t ext = (uint64_t)'P' | (uint64_t)'C' << 8 | (uint64_t)(4 + 4 * ix.K) << 16 | 1ull << 32;
+            outb[ix.crc_at - kIdxCrcFixed + (l - 20)] = (uint8_t)(ext >> (8 * (l - 20)));
+        }
+        if (ix.crcs) {
+            // every chunk's CRC-32 into its entry (crc_at is a multiple of 4), and the value's folded from them as
+            // crc32_combine does: crc = crc x^(8 clen) + crc_k -- one pass over the value, as without the switch
+            constexpr CrcX8 kX8 = make_crc_x8();
+            for (uint32_t k = 0; k < ix.K; k++) {
+                const uint64_t c0 = (uint64_t)k * L.idx_chunk;
+                const uint32_t clen = (uint32_t)(len - c0 < L.idx_chunk ? len - c0 : L.idx_chunk);
+                const uint32_t ck = wave_crc32(src + c0, clen, crc_tab);
+                if (l == 0) outw[ix.crc_at / 4 + k] = ck;
+                crc = multmodp(multmodp(crc_shift_chunks(clen >> 4), kX8.v[clen & 15]), crc) ^ ck;
+            }
         }
         sync();
         uint64_t bitpos = (uint64_t)ix.hdr * 8, pos = 0, block_start = 0, last_start = 0;

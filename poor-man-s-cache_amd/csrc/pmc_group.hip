@@ -107,6 +107,12 @@ PMC_API int pmc_group_set_index(pmc_group *g, int on) {
     return PMC_OK;
 }
 
+PMC_API int pmc_group_set_index_crc(pmc_group *g, int on) {
+    if (!g || (on != 0 && on != 1)) return PMC_E_ARG;
+    for (auto *c : g->ctx) c->index_crc = on; // (all members: the switch cannot fail on one)
+    return PMC_OK;
+}
+
 PMC_API int pmc_group_set_dictionary(pmc_group *g, const void *dict, size_t len) {
     if (!g || len > PMC_DICT_MAX) return PMC_E_ARG;
     if (!dict) len = 0;

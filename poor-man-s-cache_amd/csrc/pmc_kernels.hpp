@@ -104,6 +104,11 @@ struct LargeArgs {
     const uint64_t *seg_tok0; // [nseg] base of the segment's token buffer in tok
     const uint32_t *ch_val;   // [nch] value ordinal of sort chunk c (chunk c - lv_ch0[ov] of the value)
     uint32_t nv, nseg, nch;
+    // the emit: an indexed member of at most kIdxCrcMaxChunks chunks also carries their CRC-32s (idx_plan's crc;
+    // include/pmc_codec.h "member index", chunk CRCs); acts only where idx_chunk, below, does.  (Here it fills the
+    // four bytes in front of the pointers: no other field moves, and the kernels that do not read it keep their
+    // code.)
+    uint32_t idx_crc;
     uint32_t *tmp, *S, *R;    // position-indexed (lv_pbase): sort scratch, sorted positions, ranks
     uint8_t *HC;              // position-indexed: the nearest chain candidate exists (zlib's search runs)
     uint32_t *hist;           // [nch][256] digit counts -> scatter bases
@@ -283,13 +288,23 @@ struct RangeArgs {
     uint32_t *cnt;         // [n] chunks the request covers, 0 = answered by the scan
     const uint64_t *pre;   // [n] exclusive prefix sum of cnt: the request's first item
     const uint64_t *total; // the number of items
-    uint32_t *fail;        // [n] some covered chunk did not decode as its index says
+    // [n] bit 0: some covered chunk did not decode as its index says, or as its CRC entry says; bit 1 (set by the
+    // scan, kept by every later store): the member carries chunk CRCs
+    uint32_t *fail;
     uint64_t *counts;      // the context's three counters (pmc_ctx_range_counts)
+    uint64_t *vcounts;     // the context's two verification counters (pmc_ctx_range_verify_counts)
+    int32_t require;       // pmc_ctx_set_range_verify 1: a member without chunk CRCs is declined by the scan
+    // requests of this call that have chunks to decode in a member with chunk CRCs: counted by the scan, read by
+    // the two instances of the range kernel (one of them runs), zeroed again by the finish kernel
+    uint32_t *ncrc;
     uint8_t *rows;         // edge rows of kRangeRowBytes
     int32_t row_per_request; // rows 2 i, 2 i + 1 belong to request i; else row b * 64 + lane to the grid's lane
     int32_t off;           // PMC_INFLATE_WAVE=1: the fast paths are off, every request is declined
 };
 __global__ void inflate_range_scan_kernel(InflateArgs a, RangeArgs R);
+// kVerify false: a call without such requests (ncrc 0) -- the kernel as it was before chunk CRCs; true: any other
+// call, with the check of the decoded chunks.  Both are launched, and the one the call is not for returns at once.
+template <bool kVerify>
 __global__ void inflate_range_kernel(InflateArgs a, RangeArgs R);
 __global__ void inflate_range_finish_kernel(InflateArgs a, RangeArgs R);
 __global__ void arg_check_kernel(const uint32_t *src_len, uint64_t n, uint64_t max_len, int32_t *rc,

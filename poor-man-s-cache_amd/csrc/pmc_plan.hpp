@@ -158,20 +158,34 @@ constexpr uint32_t kIdxLog2Min = 12, kIdxLog2Max = 24;
 static_assert((kIdxChunk & (kIdxChunk - 1)) == 0 && kIdxChunk >= (1u << kIdxLog2Min) && kIdxChunk <= (1u << kIdxLog2Max),
               "index chunk size");
 
+// chunk CRCs (include/pmc_codec.h "member index", chunk CRCs): a second FEXTRA subfield 'P' 'C' of 8 + 4 K bytes
+// directly behind the 'P' 'I' one; XLEN = 8 K + 12 fits 16 bits
+constexpr uint32_t kIdxCrcMaxChunks = 8190;
+constexpr uint32_t kIdxCrcFixed = 8;               // the subfield's bytes before its K entries
+
 // What the index switch makes of a fast-all value of `len` bytes with chunks of C bytes (C 0: switch off):
-// K chunks behind a header of hdr bytes when indexed, else the plain member (K 1, hdr 10).
+// K chunks behind a header of hdr bytes when indexed, else the plain member (K 1, hdr 10).  With the chunk-CRC
+// switch (crc) an indexed value of K <= kIdxCrcMaxChunks chunks also carries their CRC-32s (crcs), at byte
+// crc_at of the member; a longer one stays the plain indexed member.
 struct IdxPlan {
     bool indexed;
     uint32_t K, hdr;
+    bool crcs;
+    uint32_t crc_at;
 };
-PMC_HD inline IdxPlan idx_plan(uint64_t len, uint32_t C) {
-    IdxPlan p{false, 1, 10};
+PMC_HD inline IdxPlan idx_plan(uint64_t len, uint32_t C, bool crc = false) {
+    IdxPlan p{false, 1, 10, false, 0};
     if (C == 0 || len <= C) return p;
     const uint64_t K = (len + C - 1) / C;
     if (K > kIdxMaxChunks) return p;
     p.indexed = true;
     p.K = (uint32_t)K;
     p.hdr = kIdxHdrFixed + 4 * (p.K - 1);
+    if (crc && p.K <= kIdxCrcMaxChunks) {
+        p.crcs = true;
+        p.crc_at = p.hdr + kIdxCrcFixed;
+        p.hdr = p.crc_at + 4 * p.K;
+    }
     return p;
 }
 
@@ -202,6 +216,27 @@ PMC_HD inline bool idx_parse(P m, uint64_t len, uint32_t *log2c, uint32_t *K, ui
     *K = k;
     *isize = isz;
     *hdr = h;
+    return true;
+}
+
+// The chunk CRCs a member carries: idx_parse holds, and the subfield 'P' 'C' lies directly behind the 'P' 'I'
+// one (at byte 16 + LEN_PI) and wholly inside the FEXTRA field, with LEN = 4 + 4 K, version 1 and three reserved
+// bytes 0.  *crc_at: the byte of chunk 0's entry (K entries of u32 LE follow).  Any other member carries none.
+// (idx_crc_sub: the subfield's own rules, for a member whose idx_parse gave k chunks and the header's end hdr)
+template <class P>
+PMC_HD inline bool idx_crc_sub(P m, uint32_t k, uint32_t hdr, uint32_t *crc_at) {
+    const uint32_t p = 16 + 4 * k; // (LEN_PI = 4 k)
+    if ((uint64_t)p + kIdxCrcFixed + 4 * (uint64_t)k > hdr) return false;
+    if (m[p] != 'P' || m[p + 1] != 'C' || ((uint32_t)m[p + 2] | (uint32_t)m[p + 3] << 8) != 4 + 4 * k) return false;
+    if (m[p + 4] != 1 || m[p + 5] != 0 || m[p + 6] != 0 || m[p + 7] != 0) return false;
+    *crc_at = p + kIdxCrcFixed;
+    return true;
+}
+template <class P>
+PMC_HD inline bool idx_crc_parse(P m, uint64_t len, uint32_t *K, uint32_t *crc_at) {
+    uint32_t lg, k, isz, hdr;
+    if (!idx_parse(m, len, &lg, &k, &isz, &hdr) || !idx_crc_sub(m, k, hdr, crc_at)) return false;
+    *K = k;
     return true;
 }
 

@@ -572,6 +572,8 @@ PMC_API int pmc_store_free(pmc_store *s, pmc_extent *ext, uint32_t n) {
     return PMC_OK;
 }
 
+PMC_API uint8_t *pmc_store_data(pmc_store *s) { return s ? (uint8_t *)s->heap.p : nullptr; }
+
 PMC_API int pmc_store_stats(pmc_store *s, uint64_t *used, uint64_t *reserved, uint64_t *heap) {
     if (!s) return PMC_E_ARG;
     std::lock_guard<std::mutex> lock(s->alloc_mu);

@@ -69,6 +69,7 @@ SIGNATURES = {
     "pmc_store_read_members": (_c.c_int, [_p, _p, _u32, _p, _p]),
     "pmc_store_free": (_c.c_int, [_p, _p, _u32]),
     "pmc_store_stats": (_c.c_int, [_p, _c.POINTER(_u64), _c.POINTER(_u64), _c.POINTER(_u64)]),
+    "pmc_store_data": (_p, [_p]),
     "pmc_slab_create": (_c.c_int, [_p, _u32, _u32, _c.POINTER(_p)]),
     "pmc_slab_destroy": (None, [_p]),
     "pmc_slab_data": (_p, [_p]),
@@ -107,6 +108,13 @@ SIGNATURES = {
     "pmc_gzip_decompress_range_batch": (_c.c_int, [_p, _p, _p, _p, _p, _p, _u32, _p, _p, _p, _p, _p, _p]),
     "pmc_ctx_range_counts": (_c.c_int, [_p, _c.POINTER(_u64)]),
     "pmc_store_get_range_batch": (_c.c_int, [_p, _p, _p, _p, _u32, _c.c_int, _p, _p, _p]),
+    "pmc_ctx_set_index_crc": (_c.c_int, [_p, _c.c_int]),
+    "pmc_ctx_get_index_crc": (_c.c_int, [_p, _c.POINTER(_c.c_int)]),
+    "pmc_group_set_index_crc": (_c.c_int, [_p, _c.c_int]),
+    "pmc_gzip_index_crc_info": (_c.c_int, [_c.c_char_p, _c.c_size_t, _c.POINTER(_u32), _u32, _c.POINTER(_u32)]),
+    "pmc_ctx_set_range_verify": (_c.c_int, [_p, _c.c_int]),
+    "pmc_ctx_get_range_verify": (_c.c_int, [_p, _c.POINTER(_c.c_int)]),
+    "pmc_ctx_range_verify_counts": (_c.c_int, [_p, _c.POINTER(_u64)]),
 }
 
 # compression levels (include/pmc_codec.h PMC_LEVEL_*)
@@ -188,6 +196,19 @@ def index_info(member: bytes):
     return c.value, k.value
 
 
+def index_crc_info(member: bytes):
+    """The chunk CRC-32s an indexed member carries (one per chunk), or None when it carries none
+    (include/pmc_codec.h pmc_gzip_index_crc_info).  Host only; the stream is not checked."""
+    member = bytes(member)
+    k = _u32(0)
+    if lib().pmc_gzip_index_crc_info(member, len(member), None, 0, ctypes.byref(k)) != E_CAPACITY:
+        return None  # (a valid subfield has K >= 2 entries, so a capacity of 0 never suffices)
+    crcs = (_u32 * k.value)()
+    if lib().pmc_gzip_index_crc_info(member, len(member), crcs, k.value, ctypes.byref(k)) != 0:
+        return None
+    return list(crcs)
+
+
 def decompress_capacity(member: bytes) -> int:
     """Output capacity for one gzip member: its ISIZE trailer, clamped to DEFLATE's
     1032:1 maximum expansion (a larger ISIZE cannot belong to a valid member)."""
@@ -241,6 +262,48 @@ class Context:
         rc = lib().pmc_ctx_set_index(self.handle, int(on))
         if rc != 0:
             raise ValueError(f"pmc_ctx_set_index({on}) = {rc}")
+
+    @property
+    def index_crc(self) -> bool:
+        """The chunk-CRC switch (include/pmc_codec.h "member index", chunk CRCs): with it and the index switch on,
+        indexed members of at most 8190 chunks also carry every chunk's CRC-32, which ranged reads check.
+        Setting it takes effect for the calls issued afterwards."""
+        v = _c.c_int(0)
+        rc = lib().pmc_ctx_get_index_crc(self.handle, ctypes.byref(v))
+        if rc != 0:
+            raise CodecUnavailable(f"pmc_ctx_get_index_crc failed ({rc})")
+        return bool(v.value)
+
+    @index_crc.setter
+    def index_crc(self, on):
+        rc = lib().pmc_ctx_set_index_crc(self.handle, int(on))
+        if rc != 0:
+            raise ValueError(f"pmc_ctx_set_index_crc({on}) = {rc}")
+
+    @property
+    def range_verify(self) -> int:
+        """How ranged reads treat chunk CRCs: 0 checks them where a member carries them, 1 also declines
+        (E_NO_INDEX) every member that carries none (include/pmc_codec.h "ranged reads", INTEGRITY)."""
+        v = _c.c_int(0)
+        rc = lib().pmc_ctx_get_range_verify(self.handle, ctypes.byref(v))
+        if rc != 0:
+            raise CodecUnavailable(f"pmc_ctx_get_range_verify failed ({rc})")
+        return v.value
+
+    @range_verify.setter
+    def range_verify(self, mode):
+        rc = lib().pmc_ctx_set_range_verify(self.handle, int(mode))
+        if rc != 0:
+            raise ValueError(f"pmc_ctx_set_range_verify({mode}) = {rc}")
+
+    def range_verify_counts(self):
+        """{matched, mismatched}: chunks whose CRC-32 a ranged read checked and found right / wrong
+        (include/pmc_codec.h pmc_ctx_range_verify_counts)."""
+        c = (_u64 * 2)()
+        rc = lib().pmc_ctx_range_verify_counts(self.handle, c)
+        if rc != 0:
+            raise CodecUnavailable(f"pmc_ctx_range_verify_counts failed ({rc}): {last_error()}")
+        return {"matched": c[0], "mismatched": c[1]}
 
     def index_counts(self):
         """{completed, handed_over}: indexed members the chunk pass decoded / took and then left to the wave
@@ -544,6 +607,10 @@ class Store:
         u, r, h = _u64(), _u64(), _u64()
         lib().pmc_store_stats(self.handle, ctypes.byref(u), ctypes.byref(r), ctypes.byref(h))
         return {"used": u.value, "reserved": r.value, "heap": h.value}
+
+    def data_ptr(self):
+        """The heap's base (a device pointer): extent e's member lies at data_ptr() + e.off."""
+        return lib().pmc_store_data(self.handle)
 
     def close(self):
         if self.handle:

@@ -10,6 +10,7 @@ call's scan runs under `order`, its decode and finish under `inflate_lane`).
 
     python scripts/range_bench.py --n 1000 --vlen 1048576 --ranges 4096,65536,0
     python scripts/range_bench.py --n 40000 --vlen 65536 --ranges 4096,0        (0: the whole value)
+    python scripts/range_bench.py --index-crc       (members with chunk CRCs: every ranged call verifies them)
 """
 import argparse
 import ctypes
@@ -62,6 +63,8 @@ def main():
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--index-crc", action="store_true",
+                    help="write members with chunk CRCs (pmc_ctx_set_index_crc); the ranged calls then check them")
     args = ap.parse_args()
     n, vlen = args.n, args.vlen
     torch.cuda.set_device(0)
@@ -70,6 +73,8 @@ def main():
     ctx = pmc_codec.Context(0)
     ctx.level = pmc_codec.LEVEL_FAST_ALL
     ctx.index = True
+    if args.index_crc:
+        ctx.index_crc = True
     stream = torch.cuda.current_stream()
     sh = stream.cuda_stream
     corpus_b = load_corpus()
@@ -90,7 +95,10 @@ def main():
     ctx.compress_device(src, off, lens, comp, coff, ccap, clen, crc, vlen, sh)
     torch.cuda.synchronize()
     assert int((crc != 0).sum()) == 0
-    back = torch.empty(n * vlen + 16, dtype=torch.uint8, device=dev)
+    # the compress call that wrote the members, timed on its own (device events, one call per run)
+    compress_ms = [round(timed(lambda: ctx.compress_device(src, off, lens, comp, coff, ccap, clen, crc, vlen, sh), 1,
+                               stream), 4) for _ in range(args.runs)]
+    back =torch.empty(n * vlen + 16, dtype=torch.uint8, device=dev)
     blen = torch.zeros(n, dtype=torch.int32, device=dev)
     brc = torch.zeros(n, dtype=torch.int32, device=dev)
 
@@ -101,7 +109,8 @@ def main():
     torch.cuda.synchronize()
     assert int((brc != 0).sum()) == 0 and torch.equal(back[:n * vlen], src[:n * vlen])
     res = {"n": n, "vlen": vlen, "calls": args.calls, "runs": args.runs, "source_id": pmc_codec.source_id(),
-           "member_bytes_mean": float(clen.float().mean()), "legs": {}}
+           "member_bytes_mean": float(clen.double().mean()), "index_crc": bool(args.index_crc), "compress_ms": compress_ms,
+           "legs": {}}
     rng = np.random.default_rng(0x5EED)
     for rl in [int(x) for x in args.ranges.split(",")]:
         ln = rl if rl else vlen
@@ -121,6 +130,7 @@ def main():
             ctx.decompress_range_device(comp, coff, clen, roff, rlen, out, ooff, rlen, olen, orc, sh)
 
         c0 = ctx.range_counts()
+        v0 = ctx.range_verify_counts() if args.index_crc else None
         ranged()
         torch.cuda.synchronize()
         c1 = ctx.range_counts()
@@ -132,6 +142,10 @@ def main():
             assert torch.equal(out[:n * ln].view(n, ln), src[idx]), "ranged bytes differ"
             del idx
         leg = {"range_len": ln, "chunks_per_call": int(c1["chunks"] - c0["chunks"]), "ranged_ms": [], "full_ms": []}
+        if args.index_crc:  # every decoded chunk was checked, and matched
+            v1 = ctx.range_verify_counts()
+            leg["chunks_verified_per_call"] = int(v1["matched"] - v0["matched"])
+            assert leg["chunks_verified_per_call"] == leg["chunks_per_call"] and v1["mismatched"] == v0["mismatched"]
         for fn in (ranged, full):
             for _ in range(args.warmup):
                 fn()
