@@ -340,6 +340,20 @@ uint32_t pmc_gzip_isize(const void *in, size_t in_len);
  * decompress call of one context may run concurrently on two streams.
  * Compress: src_len[i] == 0 -> rc PMC_INVALID_INPUT (reference semantics).  Input bytes
  *   may contain NULs (binary safe; the single-value drop-in keeps the reference's strlen).
+ *   READS: only src[src_off[i] .. src_off[i] + src_len[i]) determines member i.  Whatever precedes or
+ *   follows a value in src -- zero padding, another value, bytes that continue it -- changes no bit of
+ *   its member, at any level, on any route; src_off may be unaligned and values may overlap.
+ *   CAPACITY: a member of `need` bytes is written if and only if need <= dst_cap[i]: then rc[i] =
+ *   PMC_OK, dst_len[i] = need and dst[dst_off[i] .. + need) holds it.  Otherwise rc[i] =
+ *   PMC_E_CAPACITY and dst_len[i] = 0 (not the size needed: size slots by pmc_gzip_bound), and
+ *   nothing is written, the slot included.
+ *   WRITES: whatever the verdict, no byte of dst outside [dst_off[i], dst_off[i] + need) of the
+ *   values with rc PMC_OK is written: not the unused tail of a slot, not a failed value's slot, not
+ *   a byte between slots.  dst_off may be unaligned, dst_cap may be 0.
+ *   (tests/test_gpu_compress_bounds.py holds every route of the table in tests/boundary_values.py to
+ *   these three paragraphs, through this call, pmc_gzip_compress_batch_host and
+ *   pmc_gzip_compress_batch_pinned; the group, store and slab entries compress through the same
+ *   kernels and are not run there.)
  * Decompress: dst_cap[i] should be >= the decompressed size (ISIZE); use
  *   pmc_gzip_isize_batch to read the trailers on device.  Bytes after a member's trailer are
  *   ignored (gzip_compressor.cpp:96).  A member that decodes past dst_cap[i] gets
@@ -366,7 +380,9 @@ int pmc_gzip_isize_batch(pmc_ctx *ctx, const uint8_t *src, const uint64_t *src_o
  * Same layout, all pointers in host memory.  Stages through pinned buffers with
  * hipMemcpyAsync H2D -> kernel -> D2H on the context's stream and waits for completion.
  * dst_off may be NULL: outputs are then packed back to back in dst (dst_off[i] = sum of
- * previous dst_cap[]). */
+ * previous dst_cap[]).  Compress keeps the device-resident call's CAPACITY and WRITES paragraphs:
+ * only [dst_off[i], dst_off[i] + dst_len[i]) of the values with rc PMC_OK is written, a value whose
+ * member does not fit dst_cap[i] gets PMC_E_CAPACITY and dst_len[i] = 0. */
 int pmc_gzip_compress_batch_host(pmc_ctx *ctx, const uint8_t *src, const uint64_t *src_off,
                                  const uint32_t *src_len, uint32_t n, uint8_t *dst,
                                  const uint64_t *dst_off, const uint32_t *dst_cap, uint32_t *dst_len,
