@@ -428,6 +428,13 @@ int pmc_gzip_decompress_batch_pinned(pmc_ctx *ctx, const uint8_t *src, const uin
  *   put: values (host memory) -> pinned staging -> H2D -> compress into the put's device staging
  *        -> lengths come back -> extents of the MEMBER's size (rounded to 16 B) are allocated and
  *        the members compacted into them on the device: the heap holds ~C bytes per value.
+ *        An extent reserves cap = the member's length rounded up to 16 B; a cap above 8192 is
+ *        rounded up again to a multiple of 1/8 of the largest power of two <= it (9216, 10240, ...,
+ *        16384, 18432, ...: bounded waste, few distinct sizes).  Freed extents wait on a free list
+ *        per exact cap, last in, first out; a request takes the newest entry of its cap's list,
+ *        else the next bytes of the heap never handed out (`reserved`, which never shrinks), else
+ *        -- no entry of that cap and less than cap bytes of heap left -- the value fails with
+ *        PMC_Z_MEM_ERROR and the allocator is unchanged.  Extents are not split or merged.
  *   get: extents -> decompress on the device into a packed response image, optionally framed
  *        as the server's wire format (f3: the custom protocol's value + 0x1F, or a RESP bulk
  *        string "$<len>\r\n<value>\r\n", /root/reference/src/server/protocol.cpp:399-406,
