@@ -245,6 +245,80 @@ int pmc_ctx_set_range_verify(pmc_ctx *ctx, int mode);
 int pmc_ctx_get_range_verify(pmc_ctx *ctx, int *mode);
 int pmc_ctx_range_verify_counts(pmc_ctx *ctx, uint64_t counts[2]);
 
+/* ---- ranged writes -----------------------------------------------------------------------------
+ * What the chunk CRCs are for on the write side: value bytes [range_off, range_off + patch_len) of an indexed
+ * member replaced by a patch, compressing again only the chunks the patch touches (csrc/pmc_deflate_patch.hip).
+ * The other chunks' compressed spans are copied verbatim -- they start on the bytes the index names -- and the new
+ * member's CRC-32 is folded from the chunk CRCs (crc32_combine's recurrence), so no untouched byte of the value
+ * is read.  Device-resident members only.
+ *
+ * pmc_gzip_rewrite_range_batch: all arrays are device pointers.  It is a compress-direction call: it uses the
+ * context's compress scratch and is ordered with the context's other compress calls.  It reads the number of
+ * touched chunks back to plan its scratch, so it waits for the stream up to that point, as a compress call with
+ * large values does; everything after that is only enqueued.  dst must not overlap src or patch.  Request i turns
+ * member i -- the encoding of a value V of S = ISIZE bytes -- into a member of V', which is V with bytes
+ * [range_off[i], range_off[i] + patch_len[i]) replaced by patch[patch_off[i] .. + patch_len[i]).  Per request, in
+ * this order:
+ *   1. Member check.  All of these must hold, or rc[i] = PMC_E_NO_INDEX, dst_len[i] = 0 and nothing is written:
+ *      the member carries a valid index by the rules of pmc_gzip_index_info; its log2 C is this library's own
+ *      chunk size (15: new chunks are written at that size); it carries chunk CRCs ("member index", above); the
+ *      fold of its K entries -- crc = crc x^(8 clen_k) + entry_k over k = 0 .. K-1, chunk lengths from S and C,
+ *      the recurrence the compressor uses -- equals the trailer's CRC-32; the context's create-time lane-order
+ *      probe passed (else the fast parse is not available); PMC_INFLATE_WAVE=1 is not set (with it every request
+ *      is PMC_E_NO_INDEX, as for ranged reads).
+ *   2. Bounds.  (uint64) range_off + patch_len > S: rc[i] = PMC_E_ARG, dst_len[i] = 0.  No growth, no zero
+ *      padding, no 32-bit wrap.
+ *   3. patch_len == 0: the output is the input member, byte for byte (subject to step 6's capacity rule).
+ *   4. Touched chunks: a = range_off >> 15 .. b = (range_off + patch_len - 1) >> 15.  A touched chunk the patch
+ *      covers only in part is an EDGE CHUNK (at most two per request): it is decoded whole, must pass exactly the
+ *      ranged read's structural test (step 5 there), and its CRC-32 must equal its entry; either failure gives
+ *      PMC_E_NO_INDEX.  A chunk the patch covers completely is not decoded -- its old stream is never looked at
+ *      -- and untouched chunks are neither decoded nor inspected.
+ *   5. Recompression.  The new bytes of chunks a .. b are parsed and emitted as chunks a .. b of V' ("member
+ *      index", Tokens).  A segment that fails the lane-order guard gives PMC_E_NO_INDEX (the caller's full path
+ *      redoes the value at level 9).
+ *   6. Assembly.  The new member has `need` bytes: the header of "member index" with the same K, every offset
+ *      recomputed, every CRC entry (new for the touched chunks, carried over otherwise), the K chunk spans in
+ *      order, the trailer with the CRC-32 folded from the new entries and ISIZE = S.  need > dst_cap[i]: rc[i] =
+ *      PMC_E_CAPACITY, dst_len[i] = need, nothing is written; pmc_gzip_bound(S) always suffices.  Otherwise
+ *      rc[i] = PMC_OK, dst_len[i] = need and dst[dst_off[i] .. + need) holds the member.
+ * BYTES: if the old member is what pmc_gzip_compress_batch writes for V at PMC_LEVEL_FAST_ALL with the index and
+ * index_crc switches on, then on PMC_OK the new member is byte for byte what that call writes for V' -- whatever
+ * the context's level and switches are at the time of the rewrite: a member keeps the form it has.  (A touched
+ * chunk is emitted as at its place in a value of S bytes: the same window base, block cuts every 16383 symbols,
+ * the last chunk's last block final with no empty block after a 16383rd symbol, the empty stored block behind
+ * every other chunk; so a touched chunk whose bytes did not change comes out as it was.)  For any other valid
+ * indexed member with chunk CRCs -- a foreign writer's -- the untouched chunks keep their bytes verbatim, the
+ * touched ones are this library's, and header, entries and trailer follow "member index" (FEXTRA holds the two
+ * subfields and nothing else).
+ * INTEGRITY: the call vouches for the chunks it decoded -- structure and CRC-32 -- and for nothing else.  It does
+ * not launder damage: the trailer is folded from the entries, so an untouched chunk whose stream is damaged still
+ * fails the new member's full read with PMC_Z_DATA_ERROR, and a damaged entry fails the fold of step 1.  The call
+ * never gives a corrupt-stream verdict: it answers PMC_OK, PMC_E_NO_INDEX, PMC_E_ARG or PMC_E_CAPACITY.
+ * WRITES: whatever the outcome, no byte outside [dst_off[i], dst_off[i] + need) of the requests with rc PMC_OK is
+ * written.  dst_off, src_off and patch_off may be unaligned.  Requests are independent; two may name the same
+ * source member.
+ * n == 0 returns PMC_OK; a NULL context or (n > 0) a NULL array returns PMC_E_ARG without touching a device.
+ * Scratch: 44 bytes per request, and per round at most 2 GiB whatever n and the patches are (csrc/pmc_plan.hpp
+ * plan_patch, plan_patch_round): the touched chunks are worked on in rounds of whole requests, at most 8192 chunks
+ * each (a request has at most 8190), and a touched chunk takes about 197 KiB -- its bytes, the parse's token
+ * buffers, the emitted span's slot -- beside 64 KiB per emitting wave (at most 2048); 1000 requests inside one
+ * chunk each: about 255 MiB.  The context keeps the largest
+ * scratch a call has planned until pmc_ctx_destroy, as it keeps all its scratch.
+ *
+ * pmc_ctx_rewrite_counts synchronizes the device like pmc_ctx_range_counts: counts[0] = requests answered PMC_OK,
+ * counts[1] = requests answered PMC_E_NO_INDEX, counts[2] = edge chunks given to the decoder (whatever became of
+ * their request), counts[3] = chunks compressed again and counts[4] = chunks copied verbatim, both for the requests
+ * answered PMC_OK (an empty patch copies its K chunks).
+ *
+ * (pmc_store_set_range_batch, below, is the call that always performs the write.)  Not provided: growth and APPEND
+ * (K changes), a host-memory entry point, slab, group and server wrappers, members without chunk CRCs. */
+int pmc_gzip_rewrite_range_batch(pmc_ctx *ctx, const uint8_t *src, const uint64_t *src_off, const uint32_t *src_len,
+                                 const uint8_t *patch, const uint64_t *patch_off, const uint32_t *patch_len,
+                                 const uint32_t *range_off, uint32_t n, uint8_t *dst, const uint64_t *dst_off,
+                                 const uint32_t *dst_cap, uint32_t *dst_len, int32_t *rc, void *stream);
+int pmc_ctx_rewrite_counts(pmc_ctx *ctx, uint64_t counts[5]);
+
 /* ---- preset dictionary ----------------------------------------------------------------------
  * A context holds at most one dictionary of 1 .. PMC_DICT_MAX bytes (host memory at the call, copied
  * to a device buffer the context owns).  Its id is the CRC-32 of its bytes; id 0 stands for "none".
@@ -485,6 +559,22 @@ int pmc_store_get_batch_frames(pmc_store *s, const pmc_extent *ext, uint32_t n, 
 int pmc_store_get_range_batch(pmc_store *s, const pmc_extent *ext, const uint32_t *range_off,
                               const uint32_t *range_len, uint32_t n, int frame, const uint8_t **resp,
                               uint32_t *resp_len, int32_t *rc);
+/* Bytes [range_off[i], range_off[i] + src_len[i]) of extent i's value replaced by the patch at src + src_off[i]
+ * (host memory; "ranged writes", above).  Synchronous; it takes both the put's and the get's lock.  The extents of
+ * one call must be distinct: duplicates (by off) all get PMC_E_ARG and stay as they are.  An empty or freed extent
+ * gets PMC_E_ARG, and so does range_off + src_len > raw_len (no growth); an empty patch is PMC_OK and changes
+ * nothing.  It always performs the write, for every live, in-bounds request: extents of raw_len > 32768 go through
+ * pmc_gzip_rewrite_range_batch over the heap into the put's staging (slots of pmc_gzip_bound(raw_len)); those it
+ * answers PMC_E_NO_INDEX (level-9 members, members without chunk CRCs, edge chunks that hold stored blocks) and the
+ * smaller extents are read whole by pmc_gzip_decompress_batch into device scratch, CRC-checked, patched there, and
+ * compressed by pmc_gzip_compress_batch at the context's current level and switches, in rounds of at most 64 MiB of
+ * values (csrc/pmc_plan.hpp kRangeFallbackBudget; a larger extent gets a round of its own); if that read fails the
+ * request gets its rc.  New extents are then allocated at the members' sizes, exactly as a put does, the members
+ * compacted in, and only then the old extents released: OLD AND NEW EXTENTS BRIEFLY COEXIST, so a heap with no room
+ * for the new member gives PMC_Z_MEM_ERROR.  On any failure ext[i] is unchanged and still live; on success ext[i]
+ * is the new extent, raw_len unchanged. */
+int pmc_store_set_range_batch(pmc_store *s, pmc_extent *ext, const uint8_t *src, const uint64_t *src_off,
+                              const uint32_t *src_len, const uint32_t *range_off, uint32_t n, int32_t *rc);
 /* Copy extents' compressed bytes (gzip members) to host memory: member i at dst + dst_off[i]. */
 int pmc_store_read_members(pmc_store *s, const pmc_extent *ext, uint32_t n, uint8_t *dst,
                            const uint64_t *dst_off);

@@ -201,6 +201,10 @@ struct pmc_ctx {
     // blocks per CU of inflate_range_kernel (0: not asked yet; asked under the decompress lock)
     DevBuf rng;
     int range_per_cu = 0;
+    // ranged writes (pmc_deflate_patch.hip): the request rows and a round's chunk rows (pmc_plan.hpp PatchPlan,
+    // PatchRound); resident blocks per CU of patch_decode_kernel (0: not asked yet; asked under the compress lock)
+    DevBuf pat, patr;
+    int patch_per_cu = 0;
     // preset dictionary (pmc_ctx_set_dictionary): its bytes on the device (zero padded to a multiple of 16),
     // length and id (CRC-32; 0 = none).  Written with host_mu and both dir_mu held, read under a dir_mu.
     DevBuf dict;
@@ -472,8 +476,9 @@ PMC_API int pmc_ctx_create(int device, pmc_ctx **out) {
     uint32_t probe = 0;
     // (bytes 32..47: the chunk pass's two u64 counters, pmc_ctx_index_counts; bytes 64..87: the ranged reads'
     // three, pmc_ctx_range_counts; bytes 96..111: their two verification counters, pmc_ctx_range_verify_counts;
-    // bytes 112..115: RangeArgs::ncrc of the ranged call in flight)
-    if (c->guard.ensure(128) || hipMemsetAsync(c->guard.p, 0, 128, c->stream) != hipSuccess) {
+    // bytes 112..115: RangeArgs::ncrc of the ranged call in flight; bytes 128..167: the ranged writes' five u64
+    // counters, pmc_ctx_rewrite_counts)
+    if (c->guard.ensure(192) || hipMemsetAsync(c->guard.p, 0, 192, c->stream) != hipSuccess) {
         pmc_ctx_destroy(c);
         return PMC_E_NO_DEVICE;
     }
@@ -717,6 +722,8 @@ PMC_API void pmc_ctx_destroy(pmc_ctx *c) {
     c->bigl.release();
     c->idx.release();
     c->rng.release();
+    c->pat.release();
+    c->patr.release();
     c->dict.release();
     c->guard.release();
     c->rlist.release();
@@ -1549,6 +1556,191 @@ PMC_API int pmc_ctx_range_verify_counts(pmc_ctx *ctx, uint64_t counts[2]) {
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(counts, (uint8_t *)ctx->guard.p + 96, 16, hipMemcpyDeviceToHost));
+    return PMC_OK;
+}
+
+// ---- ranged writes (pmc_deflate_patch.hip; include/pmc_codec.h "ranged writes") ----------------------------
+// plan_patch (pmc_plan.hpp) -> scan, prefix sum, the total read back; then rounds of whole requests, each of at
+// most kPatchRoundChunks touched chunks (PMC_PATCH_ROUND_CHUNKS lowers that, for tests): tables, edge decode,
+// overlay, the fast parse, emit, finish, copy.  A round's kernels are only enqueued.
+static uint64_t patch_round_chunks() {
+    static const uint64_t v = getenv("PMC_PATCH_ROUND_CHUNKS")
+                                  ? std::min<uint64_t>(std::max<uint64_t>(1, (uint64_t)atoll(getenv("PMC_PATCH_ROUND_CHUNKS"))),
+                                                       kPatchRoundChunks)
+                                  : kPatchRoundChunks;
+    return v;
+}
+
+static int rewrite_batch_body(pmc_ctx *ctx, PatchArgs P, hipStream_t st) {
+    int r = PMC_OK;
+    const uint32_t n = P.n;
+    if (!ctx->patch_per_cu) {
+        HIP_TRY(hipFuncSetAttribute((const void *)patch_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)patch_decode_lds()));
+        ctx->patch_per_cu = occupancy_blocks((const void *)patch_decode_kernel, 64, patch_decode_lds());
+    }
+    const PatchPlan Q = plan_patch(n, (uint64_t)ctx->cus, kIdxScanBlock);
+    if ((r = ctx->pat.ensure(Q.bytes))) return r;
+    uint8_t *q = (uint8_t *)ctx->pat.p;
+    uint64_t *pre = (uint64_t *)(q + Q.pre), *bsum = (uint64_t *)(q + Q.bsum);
+    P.cnt = (uint32_t *)(q + Q.cnt);
+    P.ka = (uint32_t *)(q + Q.ka);
+    P.fail = (uint32_t *)(q + Q.fail);
+    P.pfail = (int32_t *)(q + Q.pfail);
+    P.lv_val = (uint32_t *)(q + Q.lv_val);
+    P.seg0 = (uint32_t *)(q + Q.seg0);
+    P.rlen = (uint32_t *)(q + Q.rlen);
+    P.roff = (uint64_t *)(q + Q.roff);
+    P.pre = pre;
+    P.counts = (uint64_t *)((uint8_t *)ctx->guard.p + 128);
+    // (the fast parse needs the lane order the create-time probe checked; PMC_INFLATE_WAVE=1 turns the chunk
+    // decoder off, as for ranged reads)
+    P.off = !ctx->lane_order_ok || inflate_env().wave_only ? 1 : 0;
+    klaunch(ctx, PMC_K_ORDER, st, [&] {
+        hipLaunchKernelGGL(patch_scan_kernel, dim3(Q.mb), dim3(256), 0, st, P);
+        r = scan_u32(P.cnt, nullptr, n, pre, bsum, st);
+    });
+    if (r) return r; // (scan_u32 has named the launch that failed)
+    const uint32_t nb = (n + kIdxScanBlock - 1) / kIdxScanBlock;
+    uint64_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, bsum + nb, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint64_t budget = patch_round_chunks();
+    std::vector<uint64_t> hpre;
+    if (total > budget) { // several rounds: the host cuts at request boundaries
+        hpre.resize((size_t)n + 1);
+        HIP_TRY(hipMemcpy(hpre.data(), pre, 8 * (size_t)n, hipMemcpyDeviceToHost));
+        hpre[n] = total;
+    }
+    const uint64_t fwb = lv_fast_wave_bytes();
+    const Launch Lp = plan_lds(ctx, (const void *)lv_fast_parse_kernel, fwb, 1ull << 40, 0);
+    for (uint32_t v0 = 0; v0 < n;) {
+        uint32_t v1 = n;
+        uint64_t i0 = 0, items = total;
+        if (!hpre.empty()) { // requests while their chunks fit, and the first one always
+            i0 = hpre[v0];
+            v1 = v0 + 1;
+            while (v1 < n && hpre[v1 + 1] - i0 <= budget) v1++;
+            items = hpre[v1] - i0;
+        }
+        const PatchRound R = plan_patch_round(items, (uint64_t)ctx->cus);
+        if ((r = ctx->patr.ensure(R.bytes))) return r;
+        uint8_t *d = (uint8_t *)ctx->patr.p;
+        P.v0 = v0;
+        P.v1 = v1;
+        P.i0 = i0;
+        P.items = items;
+        P.stage = d + R.stage;
+        P.tok = (uint32_t *)(d + R.tok);
+        P.seg_val = (uint32_t *)(d + R.seg_val);
+        P.seg_tok0 = (uint64_t *)(d + R.seg_tok0);
+        P.seg_tok = (uint32_t *)(d + R.seg_tok);
+        P.slots = d + R.slots;
+        P.span = (uint32_t *)(d + R.span);
+        P.crc = (uint32_t *)(d + R.crc);
+        P.slabs = d + R.slabs;
+        const uint64_t nr = v1 - v0;
+        if (items) {
+            klaunch(ctx, PMC_K_ORDER, st, [&] {
+                const uint64_t nt = std::max<uint64_t>(nr, items);
+                hipLaunchKernelGGL(patch_tables_kernel, dim3((unsigned)std::min<uint64_t>((nt + 255) / 256, 4096)),
+                                   dim3(256), 0, st, P);
+            });
+            klaunch(ctx, PMC_K_INFLATE_LANE, st, [&] {
+                const uint64_t db = std::min<uint64_t>((2 * nr + 63) / 64, (uint64_t)ctx->cus * ctx->patch_per_cu);
+                hipLaunchKernelGGL(patch_decode_kernel, dim3((unsigned)std::max<uint64_t>(1, db)), dim3(64),
+                                   patch_decode_lds(), st, P);
+            });
+            // the fast parse over the regions: a request's touched chunks are its "value"
+            DeflateArgs a{};
+            a.src = P.stage;
+            a.src_off = P.roff;
+            a.src_len = P.rlen;
+            a.n = n;
+            a.cap_len = kFlCap;
+            a.wave_bytes = fwb;
+            a.guard = (uint32_t *)ctx->guard.p;
+            LargeArgs L{};
+            L.src = a.src;
+            L.src_off = a.src_off;
+            L.src_len = a.src_len;
+            L.lv_val = P.lv_val;
+            L.lv_seg0 = P.seg0;
+            L.seg_val = P.seg_val;
+            L.seg_tok0 = P.seg_tok0;
+            L.nv = n;
+            L.nseg = (uint32_t)(items * kPatchSegs);
+            L.tok = P.tok;
+            L.seg_tok = P.seg_tok;
+            L.fail = P.pfail;
+            L.xfl = 4;
+            L.idx_chunk = kIdxChunk;
+            L.idx_crc = 1;
+            klaunch(ctx, PMC_K_DEFLATE_LARGE, st, [&] {
+                hipLaunchKernelGGL(patch_overlay_kernel, dim3((unsigned)std::min<uint64_t>(items, 65535)), dim3(256), 0,
+                                   st, P);
+                const dim3 pg((unsigned)std::min<uint64_t>(Lp.blocks, (L.nseg + Lp.wpb - 1) / Lp.wpb));
+                hipLaunchKernelGGL(lv_fast_parse_kernel, pg, dim3(64 * Lp.wpb), Lp.lds, st, a, L);
+            });
+            klaunch(ctx, PMC_K_DEFLATE_LARGE_EMIT, st, [&] {
+                hipLaunchKernelGGL(patch_emit_kernel, dim3((unsigned)(R.waves / 4)), dim3(256), patch_emit_lds(4), st, P);
+            });
+        }
+        klaunch(ctx, PMC_K_DEFLATE_LARGE_EMIT, st, [&] {
+            const uint64_t fb = std::max<uint64_t>(1, std::min<uint64_t>((nr + 3) / 4, (uint64_t)ctx->cus * 8));
+            hipLaunchKernelGGL(patch_finish_kernel, dim3((unsigned)fb), dim3(256), 0, st, P);
+            // request blocks x chunk blocks: enough of the second to fill the device when the requests are few
+            const uint64_t gx = std::min<uint64_t>(nr, 16384);
+            const uint64_t gy = std::max<uint64_t>(1, std::min<uint64_t>(64, (uint64_t)ctx->cus * 8 / gx));
+            hipLaunchKernelGGL(patch_copy_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, P);
+        });
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            set_err("ranged-write kernels", e);
+            return PMC_E_NO_DEVICE;
+        }
+        v0 = v1;
+    }
+    return PMC_OK;
+}
+
+PMC_API int pmc_gzip_rewrite_range_batch(pmc_ctx *ctx, const uint8_t *src, const uint64_t *src_off,
+                                         const uint32_t *src_len, const uint8_t *patch, const uint64_t *patch_off,
+                                         const uint32_t *patch_len, const uint32_t *range_off, uint32_t n, uint8_t *dst,
+                                         const uint64_t *dst_off, const uint32_t *dst_cap, uint32_t *dst_len,
+                                         int32_t *rc, void *stream) {
+    if (!ctx || (n && (!src || !src_off || !src_len || !patch || !patch_off || !patch_len || !range_off || !dst ||
+                       !dst_off || !dst_cap || !dst_len || !rc)))
+        return PMC_E_ARG;
+    if (n == 0) return PMC_OK;
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::recursive_mutex> dir_lock(ctx->dir_mu[0]);
+    int r = dir_enter(ctx, 0, st);
+    if (r) return r;
+    PatchArgs P{};
+    P.src = src;
+    P.src_off = src_off;
+    P.src_len = src_len;
+    P.patch = patch;
+    P.patch_off = patch_off;
+    P.patch_len = patch_len;
+    P.range_off = range_off;
+    P.dst = dst;
+    P.dst_off = dst_off;
+    P.dst_cap = dst_cap;
+    P.dst_len = dst_len;
+    P.rc = rc;
+    P.n = n;
+    r = rewrite_batch_body(ctx, P, st);
+    const int r2 = dir_leave(ctx, 0, st);
+    return r ? r : r2;
+}
+
+PMC_API int pmc_ctx_rewrite_counts(pmc_ctx *ctx, uint64_t counts[5]) {
+    if (!ctx || !counts) return PMC_E_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(counts, (uint8_t *)ctx->guard.p + 128, 40, hipMemcpyDeviceToHost));
     return PMC_OK;
 }
 

@@ -295,6 +295,9 @@ struct DeflateWave {
     }
 
     // ---- block flush (_tr_flush_block) ------------------------------------------------------
+    // (kUser: the ranged-write emit, pmc_deflate_patch.hip, calls instance 1, so that the kernels here keep their
+    // own instance and their code, instruction for instruction)
+    template <int kUser = 0>
     __device__ uint64_t flush_block(uint32_t ntok, uint64_t block_start, uint64_t block_end, uint64_t B,
                                     bool last, uint64_t bitpos) {
         const int l = lane_id();

@@ -307,6 +307,51 @@ __global__ void inflate_range_scan_kernel(InflateArgs a, RangeArgs R);
 template <bool kVerify>
 __global__ void inflate_range_kernel(InflateArgs a, RangeArgs R);
 __global__ void inflate_range_finish_kernel(InflateArgs a, RangeArgs R);
+// ranged writes of indexed members (pmc_deflate_patch.hip; include/pmc_codec.h "ranged writes"): the request
+// rows (pmc_plan.hpp PatchPlan) and one round's chunk rows (PatchRound)
+struct PatchArgs {
+    const uint8_t *src;       // old members
+    const uint64_t *src_off;
+    const uint32_t *src_len;
+    const uint8_t *patch;
+    const uint64_t *patch_off;
+    const uint32_t *patch_len, *range_off;
+    uint8_t *dst;
+    const uint64_t *dst_off;
+    const uint32_t *dst_cap;
+    uint32_t *dst_len;
+    int32_t *rc;
+    uint32_t n;
+    int32_t off;              // the fast parse or the chunk decoder is not available: every request is declined
+    uint32_t *cnt;            // [n] touched chunks, 0 = answered by the scan or an empty patch
+    uint32_t *ka;             // [n] the first touched chunk
+    uint32_t *fail;           // [n] an edge chunk did not decode as its index and CRC entry say, or an emit failed
+    const uint64_t *pre;      // [n] exclusive prefix sum of cnt: the request's first chunk item
+    uint64_t *counts;         // the context's five counters (pmc_ctx_rewrite_counts)
+    // the round: requests v0 .. v1 - 1, chunk items i0 .. i0 + items - 1
+    uint32_t v0, v1;
+    uint64_t i0, items;
+    uint8_t *stage;           // [items] the new bytes of the touched chunks, kIdxChunk apart
+    uint8_t *slots;           // [items] emitted spans, kPatchSlotBytes apart
+    uint32_t *span, *crc;     // [items] span bytes (0: the emit failed), the chunk's CRC-32
+    uint8_t *slabs;           // per emitting wave: the symbol slab
+    // the fast parse's view (lv_fast_parse_kernel): a request's region of the stage is its "value"
+    uint32_t *lv_val, *seg0, *rlen; // [n] identity, first segment, region bytes
+    uint64_t *roff;           // [n] the region's offset in the stage
+    int32_t *pfail;           // [n] a segment's sort failed the lane-order guard
+    uint32_t *seg_val;        // [items * kPatchSegs] the segment's request
+    uint64_t *seg_tok0;       // [items * kPatchSegs] its token buffer
+    uint32_t *tok, *seg_tok;  // the token buffers; [segments][4] tokens parsed, begin, end
+};
+__global__ void patch_scan_kernel(PatchArgs P);
+__global__ void patch_tables_kernel(PatchArgs P);
+__global__ void patch_decode_kernel(PatchArgs P);
+__global__ void patch_overlay_kernel(PatchArgs P);
+__global__ void patch_emit_kernel(PatchArgs P);
+__global__ void patch_finish_kernel(PatchArgs P);
+__global__ void patch_copy_kernel(PatchArgs P);
+uint64_t patch_emit_lds(int waves);
+uint32_t patch_decode_lds();
 __global__ void arg_check_kernel(const uint32_t *src_len, uint64_t n, uint64_t max_len, int32_t *rc,
                                  uint32_t *dst_len);
 __global__ void lane_order_probe_kernel(uint32_t trials, uint32_t *violations);

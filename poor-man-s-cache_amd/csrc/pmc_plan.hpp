@@ -499,6 +499,126 @@ inline Route plan_route(const RouteIn &in) {
 // 5 B per 16383-symbol block; after a window slide fixed/dynamic blocks stay <= 9/8 len.
 PMC_HD inline uint64_t gzip_bound(uint64_t len) { return len + (len >> 3) + 6 * (len / 16383 + 1) + 32; }
 
+// ---- ranged writes (include/pmc_codec.h "ranged writes"; pmc_deflate_patch.hip) --------------------------
+// The bytes [off, off + len) of a value of isize bytes that a patch replaces (no growth: ok is false when the
+// patch reaches past the end; no 32-bit wrap), and the chunks of 2^lg bytes it touches: a .. b (len 0: none).
+// A touched chunk the patch covers only in part is an edge chunk (decoded before the patch is laid over it):
+// edge_a is chunk a, edge_b is chunk b where b != a.
+struct PatchOf {
+    bool ok;
+    uint32_t a, b, items;
+    bool edge_a, edge_b;
+};
+PMC_HD inline PatchOf patch_of(uint32_t isize, uint32_t lg, uint32_t off, uint32_t len) {
+    PatchOf p{};
+    p.ok = (uint64_t)off + len <= isize;
+    if (!p.ok || len == 0) return p;
+    const uint64_t end = (uint64_t)off + len, C = 1ull << lg;
+    p.a = off >> lg;
+    p.b = (uint32_t)((end - 1) >> lg);
+    p.items = p.b - p.a + 1;
+    const uint64_t be = ((uint64_t)p.b + 1) * C < isize ? ((uint64_t)p.b + 1) * C : isize; // chunk b's end
+    const bool head = (off & (C - 1)) != 0, tail = end != be;
+    p.edge_a = head || (p.a == p.b && tail);
+    p.edge_b = p.a != p.b && tail;
+    return p;
+}
+
+// The member's CRC-32 folded from its K chunk CRCs as crc32_combine does, chunk lengths from isize and C = 2^lg:
+// crc = crc * x^(8 clen) + e[k] in GF(2)[x] mod P, reflected (the host form of the emit kernel's recurrence).
+inline uint32_t crc_multmodp_host(uint32_t a, uint32_t b) {
+    uint32_t p = 0;
+    for (int k = 31; k >= 0; k--) {
+        p ^= ((a >> k) & 1u) ? b : 0u;
+        b = (b >> 1) ^ (0xEDB88320u & (0u - (b & 1u)));
+    }
+    return p;
+}
+inline uint32_t crc_x8n_host(uint64_t n) { // x^(8 n) mod P
+    uint32_t r = 0x80000000u, sq = 0x00800000u; // x^0, x^8
+    for (; n; n >>= 1) {
+        if (n & 1) r = crc_multmodp_host(sq, r);
+        sq = crc_multmodp_host(sq, sq);
+    }
+    return r;
+}
+inline uint32_t crc_fold_host(const uint32_t *e, uint32_t K, uint32_t isize, uint32_t lg) {
+    uint32_t crc = 0;
+    for (uint32_t k = 0; k < K; k++) {
+        const uint64_t c0 = (uint64_t)k << lg;
+        const uint64_t clen = isize - c0 < (1ull << lg) ? isize - c0 : (1ull << lg);
+        crc = crc_multmodp_host(crc_x8n_host(clen), crc) ^ e[k];
+    }
+    return crc;
+}
+
+// A rewrite call over n requests.  Per request 44 bytes of rows (the scan's verdict state, the prefix sum of the
+// touched chunks, the parse's tables).  The touched chunks are worked on in rounds of whole requests, at most
+// kPatchRoundChunks chunks each (a request has at most kIdxCrcMaxChunks, so every request fits a round); a round's
+// scratch per chunk is the staged bytes (C), the parse's token buffers (4 C, and 28 bytes per segment), the
+// emitted span's slot (gzip_bound(C) + 16, rounded to 16) and two words, and per emitting wave a symbol slab --
+// within kPatchScratchBudget whatever n and the patches are.
+constexpr uint64_t kPatchRoundChunks = 8192;
+constexpr uint64_t kPatchScratchBudget = 2048ull << 20;
+constexpr uint64_t kPatchSlabBytes = 65536;  // (kSlabSyms u32: pmc_kernels.hpp)
+constexpr uint64_t kPatchMaxWaves = 2048;    // emitting waves of a round
+// (gzip_bound(kIdxChunk) + 16, rounded to 16: the large-value emit's image of a value of one chunk)
+constexpr uint64_t kPatchSlotBytes =
+    ((uint64_t)kIdxChunk + (kIdxChunk >> 3) + 6 * (kIdxChunk / 16383 + 1) + 32 + 16 + 15) & ~(uint64_t)15;
+constexpr uint32_t kPatchSegs = kIdxChunk / kIdxSeg; // the parse's segments per chunk
+static_assert(kPatchRoundChunks >= kIdxCrcMaxChunks, "a request's touched chunks fit one round");
+struct PatchPlan {
+    uint32_t mb; // blocks of 256 of the request kernels
+    // rows per request: cnt | ka | fail | pfail | lv_val | seg0 | rlen (u32 each), roff | pre (u64 each), then
+    // scan_u32's block sums and the total
+    uint64_t cnt, ka, fail, pfail, lv_val, seg0, rlen, roff, pre, bsum, total, bytes;
+};
+inline PatchPlan plan_patch(uint64_t n, uint64_t cus, uint64_t scan_block) {
+    PatchPlan P{};
+    P.mb = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, cus * 8));
+    const uint64_t nb = (n + scan_block - 1) / scan_block;
+    P.cnt = 0;
+    P.ka = 4 * n;
+    P.fail = 8 * n;
+    P.pfail = 12 * n;
+    P.lv_val = 16 * n;
+    P.seg0 = 20 * n;
+    P.rlen = 24 * n;
+    P.roff = (28 * n + 7) & ~(uint64_t)7;
+    P.pre = P.roff + 8 * n;
+    P.bsum = P.pre + 8 * n;
+    P.total = P.bsum + 8 * nb; // (scan_u32: bsum[nb] is the total)
+    P.bytes = P.total + 8;
+    return P;
+}
+// A round of `items` touched chunks (<= kPatchRoundChunks) emitted by `waves` waves.
+struct PatchRound {
+    uint64_t waves;
+    uint64_t stage, tok, seg_val, seg_tok0, seg_tok, slots, span, crc, slabs, bytes;
+};
+inline PatchRound plan_patch_round(uint64_t items, uint64_t cus) {
+    PatchRound R{};
+    items = std::max<uint64_t>(1, items);
+    R.waves = std::max<uint64_t>(4, std::min<uint64_t>({(items + 3) / 4 * 4, cus * 8, kPatchMaxWaves}));
+    uint64_t o = 0;
+    auto region = [&o](uint64_t bytes) {
+        const uint64_t at = o;
+        o = (o + bytes + 255) & ~(uint64_t)255;
+        return at;
+    };
+    R.stage = region(items * kIdxChunk + 4096); // (the parse's staging and the decoder read a few bytes past a chunk)
+    R.tok = region(items * kIdxChunk * 4);
+    R.seg_val = region(items * kPatchSegs * 4);
+    R.seg_tok0 = region(items * kPatchSegs * 8);
+    R.seg_tok = region(items * kPatchSegs * 16);
+    R.slots = region(items * kPatchSlotBytes);
+    R.span = region(items * 4);
+    R.crc = region(items * 4);
+    R.slabs = region(R.waves * kPatchSlabBytes);
+    R.bytes = o;
+    return R;
+}
+
 // The one statement of the wave-only route: the batches that go through the wave-per-member kernels alone
 // instead of the lane / record pipeline (InflateIn::latency).  lat_batch / lat_max_len: the compress side's
 // latency limits (1,024 values of 4 KiB; PMC_LATENCY_BATCH / PMC_LATENCY_MAX_LEN, 0 disables the path);

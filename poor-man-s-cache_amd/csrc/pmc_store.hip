@@ -525,6 +525,208 @@ PMC_API int pmc_store_get_range_batch(pmc_store *s, const pmc_extent *ext, const
     return PMC_OK;
 }
 
+// Ranged set (include/pmc_codec.h pmc_store_set_range_batch): the rewrite call over the heap for the extents
+// that may carry an index; whole read, overlay and compress, in rounds of bounded scratch, for those it declined
+// and the small ones; then new extents by member length, the members compacted in, and the old extents released.
+PMC_API int pmc_store_set_range_batch(pmc_store *s, pmc_extent *ext, const uint8_t *src, const uint64_t *src_off,
+                                      const uint32_t *src_len, const uint32_t *range_off, uint32_t n, int32_t *rc) {
+    if (!s || (n && (!ext || !src || !src_off || !src_len || !range_off || !rc))) return PMC_E_ARG;
+    if (n == 0) return PMC_OK;
+    std::lock_guard<std::mutex> get_lock(s->get_mu);
+    StoreCall call(s, s->put_mu);
+    pmc_ctx *ctx = s->ctx;
+    // live, in-bounds, distinct extents; an empty patch changes nothing
+    std::unordered_map<uint64_t, uint32_t> seen;
+    for (uint32_t i = 0; i < n; i++) {
+        const bool live = (ext[i].flags & 1) && ext[i].len;
+        rc[i] = live && (uint64_t)range_off[i] + src_len[i] <= ext[i].raw_len ? PMC_OK : PMC_E_ARG;
+        if (live) seen[ext[i].off]++;
+    }
+    std::vector<uint32_t> pick, full; // pick: chunk-path requests first, then the small ones
+    for (uint32_t i = 0; i < n; i++) {
+        if ((ext[i].flags & 1) && ext[i].len && seen[ext[i].off] > 1) rc[i] = PMC_E_ARG;
+        if (rc[i] == PMC_OK && src_len[i] && ext[i].raw_len > kIdxChunk) pick.push_back(i);
+    }
+    const uint32_t mc = (uint32_t)pick.size();
+    for (uint32_t i = 0; i < n; i++)
+        if (rc[i] == PMC_OK && src_len[i] && ext[i].raw_len <= kIdxChunk) pick.push_back(i);
+    const uint32_t m = (uint32_t)pick.size();
+    if (m == 0) return PMC_OK;
+    auto fail_all = [&](int code) { // nothing was allocated or released yet
+        for (uint32_t k = 0; k < m; k++) rc[pick[k]] = code;
+        return code;
+    };
+    // put staging: soff | poff | doff | noff (u64) | slen | plen | roff | dcap | dlen | rc (u32) | patches | slots
+    const uint64_t a8 = al256(m * 8ull), a4 = al256(m * 4ull), meta = a8 * 4 + a4 * 6;
+    uint64_t pbytes = 0, slots = 0;
+    for (uint32_t k = 0; k < m; k++) {
+        pbytes += src_len[pick[k]];
+        slots += (gzip_bound(ext[pick[k]].raw_len) + 15) & ~(uint64_t)15;
+    }
+    const uint64_t pb = al256(pbytes + 16);
+    int r = s->phost.ensure(meta + pb);
+    if (!r) r = s->pdev.ensure(meta + pb + slots + 64);
+    if (r) return fail_all(r);
+    uint8_t *hp = (uint8_t *)s->phost.p, *dp = (uint8_t *)s->pdev.p;
+    uint64_t *h_soff = (uint64_t *)hp, *h_poff = (uint64_t *)(hp + a8), *h_doff = (uint64_t *)(hp + a8 * 2);
+    uint64_t *h_noff = (uint64_t *)(hp + a8 * 3);
+    uint32_t *h_slen = (uint32_t *)(hp + a8 * 4), *h_plen = (uint32_t *)(hp + a8 * 4 + a4);
+    uint32_t *h_roff = (uint32_t *)(hp + a8 * 4 + a4 * 2), *h_dcap = (uint32_t *)(hp + a8 * 4 + a4 * 3);
+    uint32_t *h_dlen = (uint32_t *)(hp + a8 * 4 + a4 * 4);
+    int32_t *h_rc = (int32_t *)(hp + a8 * 4 + a4 * 5);
+    uint8_t *h_patch = hp + meta, *d_patch = dp + meta, *d_slots = dp + meta + pb;
+    const uint64_t d_base = (uint64_t)(dp - hp);
+    auto dev = [&](void *h) { return (uint8_t *)h + d_base; };
+    uint64_t po = 0, doff = 0;
+    for (uint32_t k = 0; k < m; k++) {
+        const uint32_t i = pick[k];
+        h_soff[k] = ext[i].off;
+        h_slen[k] = ext[i].len;
+        h_poff[k] = po;
+        h_plen[k] = src_len[i];
+        h_roff[k] = range_off[i];
+        memcpy(h_patch + po, src + src_off[i], src_len[i]);
+        po += src_len[i];
+        h_doff[k] = doff;
+        h_dcap[k] = (uint32_t)gzip_bound(ext[i].raw_len);
+        doff += (gzip_bound(ext[i].raw_len) + 15) & ~(uint64_t)15;
+        h_dlen[k] = 0;
+        h_rc[k] = k < mc ? PMC_OK : PMC_E_NO_INDEX; // (the small ones take the full path)
+    }
+    hipStream_t st = ctx->stream;
+    auto ok = [](hipError_t e) {
+        if (e != hipSuccess) set_err("pmc_store_set_range_batch", e);
+        return e == hipSuccess;
+    };
+    if (!ok(hipMemcpyAsync(dp, hp, meta + pbytes, hipMemcpyHostToDevice, st))) return fail_all(PMC_E_NO_DEVICE);
+    // 1. the chunk path
+    if (mc) {
+        r = pmc_gzip_rewrite_range_batch(ctx, (const uint8_t *)s->heap.p, (uint64_t *)dev(h_soff), (uint32_t *)dev(h_slen),
+                                         d_patch, (uint64_t *)dev(h_poff), (uint32_t *)dev(h_plen),
+                                         (uint32_t *)dev(h_roff), mc, d_slots, (uint64_t *)dev(h_doff),
+                                         (uint32_t *)dev(h_dcap), (uint32_t *)dev(h_dlen), (int32_t *)dev(h_rc), st);
+        if (r) return fail_all(r);
+        if (!ok(hipMemcpyAsync(h_dlen, dev(h_dlen), mc * 4ull, hipMemcpyDeviceToHost, st)) ||
+            !ok(hipMemcpyAsync(h_rc, dev(h_rc), mc * 4ull, hipMemcpyDeviceToHost, st)) || !ok(hipStreamSynchronize(st)))
+            return fail_all(PMC_E_NO_DEVICE);
+    }
+    for (uint32_t k = 0; k < m; k++)
+        if (h_rc[k] == PMC_E_NO_INDEX) full.push_back(k);
+    // 2. the full path: extents while their values fit the budget, and the first one always
+    for (size_t w0 = 0; w0 < full.size();) {
+        size_t w1 = w0;
+        uint64_t bytes = 0, max_raw = 1;
+        while (w1 < full.size()) {
+            const uint64_t need = ((uint64_t)ext[pick[full[w1]]].raw_len + 15) & ~(uint64_t)15;
+            if (w1 > w0 && bytes + need > kRangeFallbackBudget) break;
+            bytes += need;
+            max_raw = std::max<uint64_t>(max_raw, ext[pick[full[w1]]].raw_len);
+            w1++;
+        }
+        const uint32_t q = (uint32_t)(w1 - w0);
+        // round staging: soff | voff | cut | poff | doff (u64) | slen | vcap | vlen | vrc | plen | dcap | dlen | rc (u32) |
+        // values
+        const uint64_t b8 = al256(q * 8ull), b4 = al256(q * 4ull), rmeta = b8 * 5 + b4 * 8;
+        r = s->rhost.ensure(rmeta);
+        if (!r) r = s->rdev.ensure(rmeta + bytes + 64);
+        if (r) return fail_all(r);
+        uint8_t *rh = (uint8_t *)s->rhost.p, *rd = (uint8_t *)s->rdev.p;
+        uint64_t *g_soff = (uint64_t *)rh, *g_voff = (uint64_t *)(rh + b8), *g_cut = (uint64_t *)(rh + b8 * 2);
+        uint64_t *g_poff = (uint64_t *)(rh + b8 * 3), *g_doff = (uint64_t *)(rh + b8 * 4);
+        uint32_t *g_slen = (uint32_t *)(rh + b8 * 5), *g_vcap = (uint32_t *)(rh + b8 * 5 + b4);
+        uint32_t *g_vlen = (uint32_t *)(rh + b8 * 5 + b4 * 2);
+        int32_t *g_vrc = (int32_t *)(rh + b8 * 5 + b4 * 3);
+        uint32_t *g_plen = (uint32_t *)(rh + b8 * 5 + b4 * 4), *g_dcap = (uint32_t *)(rh + b8 * 5 + b4 * 5);
+        uint32_t *g_dlen = (uint32_t *)(rh + b8 * 5 + b4 * 6);
+        int32_t *g_rc = (int32_t *)(rh + b8 * 5 + b4 * 7);
+        const uint64_t r_base = (uint64_t)(rd - rh);
+        auto rdev = [&](void *h) { return (uint8_t *)h + r_base; };
+        uint64_t at = 0;
+        for (uint32_t j = 0; j < q; j++) {
+            const uint32_t k = full[w0 + j], i = pick[k];
+            g_soff[j] = ext[i].off;
+            g_slen[j] = ext[i].len;
+            g_voff[j] = at;
+            g_vcap[j] = ext[i].raw_len;
+            g_cut[j] = at + range_off[i];
+            g_poff[j] = h_poff[k];
+            g_plen[j] = src_len[i];
+            g_doff[j] = h_doff[k];
+            g_dcap[j] = h_dcap[k];
+            at += ((uint64_t)ext[i].raw_len + 15) & ~(uint64_t)15;
+        }
+        uint8_t *d_vals = rd + rmeta;
+        if (!ok(hipMemcpyAsync(rd, rh, rmeta, hipMemcpyHostToDevice, st))) return fail_all(PMC_E_NO_DEVICE);
+        r = pmc_gzip_decompress_batch(ctx, (const uint8_t *)s->heap.p, (uint64_t *)rdev(g_soff), (uint32_t *)rdev(g_slen), q,
+                                      d_vals, (uint64_t *)rdev(g_voff), (uint32_t *)rdev(g_vcap), (uint32_t *)rdev(g_vlen),
+                                      (int32_t *)rdev(g_vrc), (uint32_t)max_raw, st);
+        if (r) return fail_all(r);
+        // the patches over the values that decoded (rc 0), then the values compressed into their slots
+        hipLaunchKernelGGL(compact_kernel, dim3(std::min<uint32_t>((q + 3) / 4, 8192)), dim3(256), 0, st,
+                           (const uint8_t *)d_patch, (const uint64_t *)rdev(g_poff), (const uint32_t *)rdev(g_plen),
+                           (const int32_t *)rdev(g_vrc), (const uint64_t *)rdev(g_cut), q, d_vals);
+        if (!ok(hipGetLastError())) return fail_all(PMC_E_NO_DEVICE);
+        r = pmc_gzip_compress_batch(ctx, d_vals, (uint64_t *)rdev(g_voff), (uint32_t *)rdev(g_vcap), q, d_slots,
+                                    (uint64_t *)rdev(g_doff), (uint32_t *)rdev(g_dcap), (uint32_t *)rdev(g_dlen),
+                                    (int32_t *)rdev(g_rc), (uint32_t)max_raw, st);
+        if (r) return fail_all(r);
+        if (!ok(hipMemcpyAsync(g_vlen, rdev(g_vlen), b4 * 2, hipMemcpyDeviceToHost, st)) ||
+            !ok(hipMemcpyAsync(g_dlen, rdev(g_dlen), b4 * 2, hipMemcpyDeviceToHost, st)) || !ok(hipStreamSynchronize(st)))
+            return fail_all(PMC_E_NO_DEVICE);
+        for (uint32_t j = 0; j < q; j++) {
+            const uint32_t k = full[w0 + j], i = pick[k];
+            if (g_vrc[j] != PMC_OK || g_vlen[j] != ext[i].raw_len) h_rc[k] = g_vrc[j] != PMC_OK ? g_vrc[j] : PMC_Z_DATA_ERROR;
+            else h_rc[k] = g_rc[j];
+            h_dlen[k] = g_dlen[j];
+        }
+        w0 = w1;
+    }
+    // 3. new extents by member length (the old ones stay until the members are in)
+    std::vector<pmc_extent> fresh(m, pmc_extent{0, 0, 0, 0, 0});
+    {
+        std::lock_guard<std::mutex> a(s->alloc_mu);
+        for (uint32_t k = 0; k < m; k++) {
+            const uint32_t i = pick[k];
+            h_noff[k] = 0;
+            if (h_rc[k] != PMC_OK) {
+                rc[i] = h_rc[k];
+                continue;
+            }
+            const uint32_t size = extent_size(h_dlen[k]);
+            uint64_t off = 0;
+            if (!store_alloc(s, size, &off)) {
+                rc[i] = h_rc[k] = PMC_Z_MEM_ERROR; // the compact pass skips it
+                continue;
+            }
+            fresh[k] = pmc_extent{off, size, h_dlen[k], ext[i].raw_len, 1};
+            h_noff[k] = off;
+        }
+    }
+    // 4. members from the slots into the new extents
+    bool moved = ok(hipMemcpyAsync(dev(h_noff), h_noff, m * 8ull, hipMemcpyHostToDevice, st)) &&
+                 ok(hipMemcpyAsync(dev(h_rc), h_rc, m * 4ull, hipMemcpyHostToDevice, st)) &&
+                 ok(hipMemcpyAsync(dev(h_dlen), h_dlen, m * 4ull, hipMemcpyHostToDevice, st));
+    if (moved) {
+        hipLaunchKernelGGL(compact_kernel, dim3(std::min<uint32_t>((m + 3) / 4, 8192)), dim3(256), 0, st,
+                           (const uint8_t *)d_slots, (const uint64_t *)dev(h_doff), (const uint32_t *)dev(h_dlen),
+                           (const int32_t *)dev(h_rc), (const uint64_t *)dev(h_noff), m, (uint8_t *)s->heap.p);
+        moved = ok(hipGetLastError()) && ok(hipStreamSynchronize(st));
+    }
+    std::lock_guard<std::mutex> a(s->alloc_mu);
+    for (uint32_t k = 0; k < m; k++) {
+        const uint32_t i = pick[k];
+        if (!(fresh[k].flags & 1)) continue;
+        if (!moved) { // the new extents hold nothing: the old ones stay
+            store_release(s, fresh[k]);
+            rc[i] = PMC_E_NO_DEVICE;
+            continue;
+        }
+        store_release(s, ext[i]);
+        ext[i] = fresh[k];
+    }
+    return moved ? PMC_OK : PMC_E_NO_DEVICE;
+}
+
 PMC_API int pmc_store_read_members(pmc_store *s, const pmc_extent *ext, uint32_t n, uint8_t *dst,
                                    const uint64_t *dst_off) {
     if (!s || (n && (!ext || !dst || !dst_off))) return PMC_E_ARG;

@@ -115,6 +115,9 @@ SIGNATURES = {
     "pmc_ctx_set_range_verify": (_c.c_int, [_p, _c.c_int]),
     "pmc_ctx_get_range_verify": (_c.c_int, [_p, _c.POINTER(_c.c_int)]),
     "pmc_ctx_range_verify_counts": (_c.c_int, [_p, _c.POINTER(_u64)]),
+    "pmc_gzip_rewrite_range_batch": (_c.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _u32, _p, _p, _p, _p, _p, _p]),
+    "pmc_ctx_rewrite_counts": (_c.c_int, [_p, _c.POINTER(_u64)]),
+    "pmc_store_set_range_batch": (_c.c_int, [_p, _p, _p, _p, _p, _p, _u32, _p]),
 }
 
 # compression levels (include/pmc_codec.h PMC_LEVEL_*)
@@ -470,6 +473,26 @@ class Context:
         if r != 0:
             raise CodecUnavailable(f"pmc_gzip_decompress_range_batch = {r}: {last_error()}")
 
+    def rewrite_range_device(self, src, src_off, src_len, patch, patch_off, patch_len, range_off, dst, dst_off, dst_cap,
+                             dst_len, rc, stream=0):
+        """Member i with value bytes [range_off, range_off + patch_len) replaced by patch i: only the chunks the
+        patch touches are compressed again, the others are copied (include/pmc_codec.h "ranged writes").  Device
+        tensors; the call reads one number back before it enqueues its rounds."""
+        r = lib().pmc_gzip_rewrite_range_batch(self.handle, _ptr(src), _ptr(src_off), _ptr(src_len), _ptr(patch),
+                                               _ptr(patch_off), _ptr(patch_len), _ptr(range_off), _n(src_len),
+                                               _ptr(dst), _ptr(dst_off), _ptr(dst_cap), _ptr(dst_len), _ptr(rc), stream)
+        if r != 0:
+            raise CodecUnavailable(f"pmc_gzip_rewrite_range_batch = {r}: {last_error()}")
+
+    def rewrite_counts(self):
+        """{served, declined, decoded, compressed, copied}: rewrite requests answered OK / answered E_NO_INDEX, and
+        the chunks decoded, compressed again and copied verbatim (include/pmc_codec.h pmc_ctx_rewrite_counts)."""
+        c = (_u64 * 5)()
+        rc = lib().pmc_ctx_rewrite_counts(self.handle, c)
+        if rc != 0:
+            raise CodecUnavailable(f"pmc_ctx_rewrite_counts failed ({rc}): {last_error()}")
+        return {"served": c[0], "declined": c[1], "decoded": c[2], "compressed": c[3], "copied": c[4]}
+
     # ---------------- pinned host batches, pipelined over copy streams --------------
     def compress_pinned(self, src, src_off, src_len, dst, dst_off, dst_cap, dst_len, rc, max_len, chunk=0):
         """All tensor arguments are pinned CPU tensors (torch pin_memory=True)."""
@@ -585,6 +608,27 @@ class Store:
         if r != 0:
             raise CodecUnavailable(f"pmc_store_get_range_batch = {r}: {last_error()}")
         return [(int(rc[i]), ctypes.string_at(resp[i], int(plen[i])) if rc[i] == 0 else b"") for i in range(n)]
+
+    def set_range(self, ext, patches, n=None):
+        """patches: n pairs (offset, bytes): value bytes [offset, offset + len(bytes)) of extent i replaced, no growth
+        -> rc list; ext[i] becomes the new extent where rc is 0 and stays as it is otherwise.  Compresses only the
+        chunks a patch touches where the member is indexed with chunk CRCs, the whole value otherwise
+        (pmc_store_set_range_batch)."""
+        import numpy as np
+        n = len(ext) if n is None else n
+        if n == 0:
+            return []
+        assert len(patches) == n, (len(patches), n)
+        lens = np.array([len(p[1]) for p in patches], dtype=np.uint32)
+        off = np.zeros(n, dtype=np.uint64)
+        off[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+        roff = np.array([p[0] for p in patches], dtype=np.uint32)
+        rc = np.zeros(n, dtype=np.int32)
+        r = lib().pmc_store_set_range_batch(self.handle, ext, b"".join(bytes(p[1]) for p in patches) + b"\0",
+                                            off.ctypes.data, lens.ctypes.data, roff.ctypes.data, n, rc.ctypes.data)
+        if r != 0:
+            raise CodecUnavailable(f"pmc_store_set_range_batch = {r}: {last_error()}")
+        return [int(x) for x in rc]
 
     def members(self, ext, n=None):
         import numpy as np
