@@ -9,6 +9,8 @@
 
 #include <thread>
 
+#include "pmc_store_plan.hpp"
+
 // MurmurHash3_x64_128(key, len, seed 0), first 64-bit word: the reference's hashFunc
 // (hash.cpp:4-9 over MurmurHash3.cpp:255-332), restated for the host side of the route.
 namespace {
@@ -193,16 +195,16 @@ int group_share(pmc_group *g, int k, Dir dir, const std::vector<uint32_t> &idx, 
         in_b += src_len[i];
         out_b += dst_cap[i];
     }
-    const uint64_t meta = al256(m * 8ull) * 2 + al256(m * 4ull) * 4;
+    // pinned staging (host only): GetStage's arrays | values | outputs
+    const uint64_t meta = GetStage(m).meta;
     HostBuf &hb = g->share[k].buf;
     int r = hb.ensure(meta + al256(in_b + 16) + out_b + 64);
     if (r) return r;
     uint8_t *hp = (uint8_t *)hb.p;
-    uint64_t *soff = (uint64_t *)hp, *doff = (uint64_t *)(hp + al256(m * 8ull));
-    uint32_t *slen = (uint32_t *)(hp + al256(m * 8ull) * 2);
-    uint32_t *dcap = (uint32_t *)((uint8_t *)slen + al256(m * 4ull));
-    uint32_t *dlen = (uint32_t *)((uint8_t *)dcap + al256(m * 4ull));
-    int32_t *src_rc = (int32_t *)((uint8_t *)dlen + al256(m * 4ull));
+    const GetStage L(m, hp);
+    uint64_t *soff = L.soff.h, *doff = L.doff.h;
+    uint32_t *slen = L.slen.h, *dcap = L.dcap.h, *dlen = L.dlen.h;
+    int32_t *src_rc = L.rc.h;
     uint8_t *s = hp + meta, *d = s + al256(in_b + 16);
     uint64_t so = 0, dof = 0;
     for (uint32_t j = 0; j < m; j++) {

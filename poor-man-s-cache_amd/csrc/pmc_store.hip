@@ -12,10 +12,12 @@
 //     bytes are never copied on the host (f3).
 // The heap allocator is host-side: extents of the member's compressed length rounded to 16 B (to 1/8
 // of a power of two above 8 KiB), per-size free lists, bump allocation otherwise.  A put compresses
-// into gzip_bound slots of its device staging, learns the lengths, allocates, then compacts.  Compiled into the unity TU after
-// pmc_capi.hip (uses pmc_ctx, DevBuf, HostBuf, the scan/compact kernels).
+// into gzip_bound slots of its device staging, learns the lengths, allocates, then compacts.
+// Everything here that is arithmetic -- the allocator, the staging layouts, the framing, the fallback
+// rounds -- is pmc_store_plan.hpp's.  Compiled into the unity TU after pmc_capi.hip (uses pmc_ctx,
+// DevBuf, HostBuf, the scan/compact kernels).
 
-#include <unordered_map>
+#include "pmc_store_plan.hpp"
 
 // A put (compress, on the context's stream) and a get (decompress, on the store's own stream) may
 // run at the same time from two threads: each direction has its own lock and staging buffers; the
@@ -26,8 +28,7 @@ struct pmc_store {
     std::mutex put_mu, get_mu, alloc_mu;
     hipStream_t gst = nullptr;  // get / read_members stream
     DevBuf heap;
-    uint64_t heap_bytes = 0, bump = 0, used = 0;
-    std::unordered_map<uint32_t, std::vector<uint64_t>> free_lists;  // extent size -> offsets
+    StoreHeap alloc;      // which bytes of `heap` are whose (alloc_mu held)
     DevBuf pdev, gdev;    // device side of a put / a get: arrays + value bytes / response image
     HostBuf phost, ghost; // pinned host side of a put / the arrays of a get
     HostBuf hresp;        // pinned response image of the last get (resp[] points here)
@@ -36,40 +37,6 @@ struct pmc_store {
 };
 
 namespace {
-
-// bytes reserved for a member of `len` bytes: 16-byte granules, and above 8 KiB steps of 1/8 of
-// the power of two below (bounded waste, few distinct free-list sizes)
-uint32_t extent_size(uint64_t len) {
-    uint64_t c = (len + 15) & ~(uint64_t)15;
-    if (c > 8192) {
-        uint64_t p = 1;
-        while (p * 2 <= c) p *= 2;
-        const uint64_t step = p / 8;
-        c = (c + step - 1) / step * step;
-    }
-    return (uint32_t)c;
-}
-
-bool store_alloc(pmc_store *s, uint32_t size, uint64_t *off) {  // alloc_mu held
-    auto it = s->free_lists.find(size);
-    if (it != s->free_lists.end() && !it->second.empty()) {
-        *off = it->second.back();
-        it->second.pop_back();
-    } else {
-        if (s->bump + size > s->heap_bytes) return false;
-        *off = s->bump;
-        s->bump += size;
-    }
-    s->used += size;
-    return true;
-}
-
-void store_release(pmc_store *s, pmc_extent &e) {  // alloc_mu held
-    if (!(e.flags & 1)) return;
-    s->free_lists[e.cap].push_back(e.off);
-    s->used -= e.cap;
-    e.flags = 0;
-}
 
 struct StoreCall {  // one direction's lock + the caller's device restored afterwards
     std::lock_guard<std::mutex> lock;
@@ -83,7 +50,69 @@ struct StoreCall {  // one direction's lock + the caller's device restored after
     }
 };
 
-inline uint64_t al256(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
+// a HIP call's verdict, a failure recorded under the entry point's name
+struct HipOk {
+    const char *who;
+    bool operator()(hipError_t e) const {
+        if (e != hipSuccess) set_err(who, e);
+        return e == hipSuccess;
+    }
+};
+
+// compact_kernel over m items (device arrays): len[k] bytes from src + from[k] to dst + to[k] where rc[k] is 0
+void launch_compact(hipStream_t st, uint32_t m, const uint8_t *src, const uint64_t *from, const uint32_t *len,
+                    const int32_t *rc, const uint64_t *to, uint8_t *dst) {
+    hipLaunchKernelGGL(compact_kernel, dim3(std::min<uint32_t>((m + 3) / 4, 8192)), dim3(256), 0, st, src, from, len, rc,
+                       to, m, dst);
+}
+
+// a decode's verdict for a value of `want` bytes: its rc, and PMC_Z_DATA_ERROR where it decoded to another length
+inline int32_t read_verdict(int32_t rc, uint32_t got, uint32_t want) {
+    return rc != PMC_OK ? rc : got != want ? PMC_Z_DATA_ERROR : PMC_OK;
+}
+
+// The step a put and a ranged set end with.  The members of the call's m values lie in their slots (d_slots +
+// doff[k], dlen[k] bytes, verdict rc[k]; lengths and verdicts are on the host).  Every value of rc 0 gets an
+// extent by its member's length: at(k) is where the extent is written, raw(k) the value's raw length; a full heap
+// makes its rc PMC_Z_MEM_ERROR, which the compact pass skips.  Then the extents' offsets (noff) and the verdicts
+// go up -- with up_dlen the lengths too -- and the members are compacted into the heap.  False where that failed:
+// the new extents hold nothing, so they are released again and their values' rc becomes PMC_E_NO_DEVICE.
+template <class ExtAt, class RawOf>
+bool store_commit(pmc_store *s, HipOk ok, hipStream_t st, uint32_t m, const uint8_t *d_slots,
+                  const StageArr<uint64_t> &doff, const StageArr<uint32_t> &dlen, const StageArr<int32_t> &rc,
+                  const StageArr<uint64_t> &noff, bool up_dlen, ExtAt at, RawOf raw) {
+    {
+        std::lock_guard<std::mutex> a(s->alloc_mu);
+        for (uint32_t k = 0; k < m; k++) {
+            noff.h[k] = 0;
+            if (rc.h[k] != PMC_OK) continue;
+            const uint32_t size = StoreHeap::extent_size(dlen.h[k]);
+            uint64_t off = 0;
+            if (!s->alloc.alloc(size, &off)) {
+                rc.h[k] = PMC_Z_MEM_ERROR;
+                continue;
+            }
+            at(k) = pmc_extent{off, size, dlen.h[k], raw(k), 1};
+            noff.h[k] = off;
+        }
+    }
+    bool moved = ok(hipMemcpyAsync(noff.d, noff.h, m * 8ull, hipMemcpyHostToDevice, st)) &&
+                 ok(hipMemcpyAsync(rc.d, rc.h, m * 4ull, hipMemcpyHostToDevice, st)) &&
+                 (!up_dlen || ok(hipMemcpyAsync(dlen.d, dlen.h, m * 4ull, hipMemcpyHostToDevice, st)));
+    if (moved) {
+        launch_compact(st, m, d_slots, doff.d, dlen.d, rc.d, noff.d, (uint8_t *)s->heap.p);
+        moved = ok(hipGetLastError()) && ok(hipStreamSynchronize(st));
+    }
+    if (!moved) {
+        std::lock_guard<std::mutex> a(s->alloc_mu);
+        for (uint32_t k = 0; k < m; k++)
+            if (rc.h[k] == PMC_OK) {
+                s->alloc.release(at(k));
+                rc.h[k] = PMC_E_NO_DEVICE;
+            }
+    }
+    return moved;
+}
 
 } // namespace
 
@@ -104,7 +133,7 @@ PMC_API int pmc_store_create(pmc_ctx *ctx, uint64_t heap_bytes, pmc_store **out)
         delete s;
         return PMC_E_NO_DEVICE;
     }
-    s->heap_bytes = heap_bytes;
+    s->alloc.heap_bytes = heap_bytes;
     *out = s;
     return PMC_OK;
 }
@@ -150,7 +179,7 @@ PMC_API int pmc_store_put_batch(pmc_store *s, const uint8_t *src, const uint64_t
         rc[i] = PMC_OK;
         pick.push_back(i);
         bytes += src_len[i];
-        slots += (gzip_bound(src_len[i]) + 15) & ~(uint64_t)15;
+        slots += round16(gzip_bound(src_len[i]));
         max_len = std::max<uint64_t>(max_len, src_len[i]);
     }
     const uint32_t m = (uint32_t)pick.size();
@@ -159,86 +188,42 @@ PMC_API int pmc_store_put_batch(pmc_store *s, const uint8_t *src, const uint64_t
         for (uint32_t k = 0; k < m; k++) rc[pick[k]] = code;
         return code;
     };
-    // staging: soff | doff | poff (u64) | slen | dcap | dlen | rc (u32) | value bytes | member slots
-    const uint64_t meta = al256(m * 8ull) * 3 + al256(m * 4ull) * 4;
-    const uint64_t vb = al256(bytes + 16);
+    // staging: PutStage's arrays | value bytes | member slots (device only)
+    const uint64_t meta = PutStage(m).meta, vb = al256(bytes + 16);
     int r = s->phost.ensure(meta + vb);
     if (!r) r = s->pdev.ensure(meta + vb + slots + 64);
     if (r) return fail_all(r);
     uint8_t *hp = (uint8_t *)s->phost.p, *dp = (uint8_t *)s->pdev.p;
-    uint64_t *h_soff = (uint64_t *)hp, *h_doff = (uint64_t *)(hp + al256(m * 8ull));
-    uint64_t *h_poff = (uint64_t *)(hp + al256(m * 8ull) * 2);
-    uint32_t *h_slen = (uint32_t *)(hp + al256(m * 8ull) * 3);
-    uint32_t *h_dcap = (uint32_t *)((uint8_t *)h_slen + al256(m * 4ull));
-    uint32_t *h_dlen = (uint32_t *)((uint8_t *)h_dcap + al256(m * 4ull));
-    int32_t *h_rc = (int32_t *)((uint8_t *)h_dlen + al256(m * 4ull));
-    uint8_t *h_src = hp + meta;
-    uint8_t *d_slots = dp + meta + vb;
-    const uint64_t d_base = (uint64_t)(dp - hp);  // device address = host address + d_base
-    auto dev = [&](void *h) { return (uint8_t *)h + d_base; };
+    const PutStage L(m, hp, dp);
+    uint8_t *h_src = hp + meta, *d_slots = dp + meta + vb;
     uint64_t so = 0, doff = 0;
     for (uint32_t k = 0; k < m; k++) {
         const uint32_t i = pick[k];
-        h_soff[k] = so;
-        h_slen[k] = src_len[i];
+        L.soff.h[k] = so;
+        L.slen.h[k] = src_len[i];
         memcpy(h_src + so, src + src_off[i], src_len[i]);
         so += src_len[i];
-        h_doff[k] = doff;
-        h_dcap[k] = (uint32_t)gzip_bound(src_len[i]);
-        doff += (gzip_bound(src_len[i]) + 15) & ~(uint64_t)15;
+        L.doff.h[k] = doff;
+        L.dcap.h[k] = (uint32_t)gzip_bound(src_len[i]);
+        doff += round16(gzip_bound(src_len[i]));
     }
     hipStream_t st = ctx->stream;
-    auto ok = [](hipError_t e) {
-        if (e != hipSuccess) set_err("pmc_store_put_batch", e);
-        return e == hipSuccess;
-    };
+    const HipOk ok{"pmc_store_put_batch"};
     // 1. values in, members into the staging slots, lengths back
     if (!ok(hipMemcpyAsync(dp, hp, meta + bytes, hipMemcpyHostToDevice, st))) return fail_all(PMC_E_NO_DEVICE);
-    r = pmc_gzip_compress_batch(ctx, dev(h_src), (uint64_t *)dev(h_soff), (uint32_t *)dev(h_slen), m, d_slots,
-                                (uint64_t *)dev(h_doff), (uint32_t *)dev(h_dcap), (uint32_t *)dev(h_dlen),
-                                (int32_t *)dev(h_rc), (uint32_t)max_len, st);
+    r = pmc_gzip_compress_batch(ctx, dp + meta, L.soff.d, L.slen.d, m, d_slots, L.doff.d, L.dcap.d, L.dlen.d, L.rc.d,
+                                (uint32_t)max_len, st);
     if (r) return fail_all(r);
-    if (!ok(hipMemcpyAsync(h_dlen, dev(h_dlen), al256(m * 4ull) * 2, hipMemcpyDeviceToHost, st)) ||
+    if (!ok(hipMemcpyAsync(L.dlen_rc.h, L.dlen_rc.d, L.dlen_rc.bytes, hipMemcpyDeviceToHost, st)) ||
         !ok(hipStreamSynchronize(st)))
         return fail_all(PMC_E_NO_DEVICE);
-    // 2. extents by compressed length
-    {
-        std::lock_guard<std::mutex> a(s->alloc_mu);
-        for (uint32_t k = 0; k < m; k++) {
-            const uint32_t i = pick[k];
-            if (h_rc[k] != PMC_OK) {
-                rc[i] = h_rc[k];
-                continue;
-            }
-            const uint32_t size = extent_size(h_dlen[k]);
-            uint64_t off = 0;
-            if (!store_alloc(s, size, &off)) {
-                rc[i] = h_rc[k] = PMC_Z_MEM_ERROR;  // the compact pass skips it
-                continue;
-            }
-            ext[i] = pmc_extent{off, size, h_dlen[k], src_len[i], 1};
-            h_poff[k] = off;
-        }
-    }
-    // 3. members from the slots into their extents (one H2D of the extent offsets and verdicts)
-    bool moved = ok(hipMemcpyAsync(dev(h_poff), h_poff, m * 8ull, hipMemcpyHostToDevice, st)) &&
-                 ok(hipMemcpyAsync(dev(h_rc), h_rc, m * 4ull, hipMemcpyHostToDevice, st));
-    if (moved) {
-        hipLaunchKernelGGL(compact_kernel, dim3(std::min<uint32_t>((m + 3) / 4, 8192)), dim3(256), 0, st,
-                           (const uint8_t *)d_slots, (const uint64_t *)dev(h_doff), (const uint32_t *)dev(h_dlen),
-                           (const int32_t *)dev(h_rc), (const uint64_t *)dev(h_poff), m, (uint8_t *)s->heap.p);
-        moved = ok(hipGetLastError()) && ok(hipStreamSynchronize(st));
-    }
-    if (!moved) {  // the extents hold nothing: release them and fail their values
-        std::lock_guard<std::mutex> a(s->alloc_mu);
-        for (uint32_t k = 0; k < m; k++) {
-            const uint32_t i = pick[k];
-            if (ext[i].flags & 1) store_release(s, ext[i]);
-            rc[i] = PMC_E_NO_DEVICE;
-        }
-        return PMC_E_NO_DEVICE;
-    }
-    return PMC_OK;
+    // 2. extents by compressed length, the members from the slots into them.  A failed compact fails every
+    // value sent to the codec, those whose compress had failed too.
+    const bool moved = store_commit(
+        s, ok, st, m, d_slots, L.doff, L.dlen, L.rc, L.poff, false, [&](uint32_t k) -> pmc_extent & { return ext[pick[k]]; },
+        [&](uint32_t k) { return src_len[pick[k]]; });
+    for (uint32_t k = 0; k < m; k++) rc[pick[k]] = moved ? L.rc.h[k] : PMC_E_NO_DEVICE;
+    return moved ? PMC_OK : PMC_E_NO_DEVICE;
 }
 
 // frame_of(i): extent i's PMC_FRAME_* (checked by the callers)
@@ -252,15 +237,6 @@ static int store_get(pmc_store *s, const pmc_extent *ext, uint32_t n, FrameOf fr
     std::vector<uint64_t> pos(n, 0);
     std::vector<uint8_t> hlen(n, 0);
     uint64_t total = 0, max_raw = 1;
-    auto digits = [](uint32_t v) {
-        uint32_t d = 1;
-        while (v >= 10) {
-            v /= 10;
-            d++;
-        }
-        return d;
-    };
-    auto tail = [](int frame) -> uint32_t { return frame == PMC_FRAME_RESP ? 2 : frame == PMC_FRAME_CUSTOM ? 1 : 0; };
     for (uint32_t i = 0; i < n; i++) {
         const int frame = frame_of(i);
         resp[i] = nullptr;
@@ -269,71 +245,46 @@ static int store_get(pmc_store *s, const pmc_extent *ext, uint32_t n, FrameOf fr
             rc[i] = PMC_E_ARG;
             continue;
         }
-        hlen[i] = (uint8_t)(frame == PMC_FRAME_RESP ? 1 + digits(ext[i].raw_len) + 2 : 0);
+        hlen[i] = (uint8_t)frame_head(frame, ext[i].raw_len);
         pos[i] = total;
-        total += hlen[i] + (uint64_t)ext[i].raw_len + tail(frame);
+        total += hlen[i] + (uint64_t)ext[i].raw_len + frame_tail(frame);
         max_raw = std::max<uint64_t>(max_raw, ext[i].raw_len);
         rc[i] = PMC_OK;
         pick.push_back(i);
     }
     const uint32_t m = (uint32_t)pick.size();
     if (m == 0) return PMC_OK;
-    // device staging: soff | doff (u64) | slen | dcap | dlen | rc (u32) | response image
-    const uint64_t meta = al256(m * 8ull) * 2 + al256(m * 4ull) * 4;
+    // device staging: GetStage's arrays | response image
+    const uint64_t meta = GetStage(m).meta;
     int r = s->ghost.ensure(meta);
     if (!r) r = s->gdev.ensure(meta + total + 64);
     if (!r) r = s->hresp.ensure(total + 64);
     if (r) return r;
     uint8_t *hp = (uint8_t *)s->ghost.p, *dp = (uint8_t *)s->gdev.p;
-    uint64_t *h_soff = (uint64_t *)hp, *h_doff = (uint64_t *)(hp + al256(m * 8ull));
-    uint32_t *h_slen = (uint32_t *)(hp + al256(m * 8ull) * 2);
-    uint32_t *h_dcap = (uint32_t *)((uint8_t *)h_slen + al256(m * 4ull));
-    uint32_t *h_dlen = (uint32_t *)((uint8_t *)h_dcap + al256(m * 4ull));
-    int32_t *h_rc = (int32_t *)((uint8_t *)h_dlen + al256(m * 4ull));
-    const uint64_t d_base = (uint64_t)(dp - hp);
-    auto dev = [&](void *h) { return (uint8_t *)h + d_base; };
+    const GetStage L(m, hp, dp);
     for (uint32_t k = 0; k < m; k++) {
         const uint32_t i = pick[k];
-        h_soff[k] = ext[i].off;
-        h_slen[k] = ext[i].len;
-        h_doff[k] = pos[i] + hlen[i];
-        h_dcap[k] = ext[i].raw_len;
+        L.soff.h[k] = ext[i].off;
+        L.slen.h[k] = ext[i].len;
+        L.doff.h[k] = pos[i] + hlen[i];
+        L.dcap.h[k] = ext[i].raw_len;
     }
     hipStream_t st = s->gst;
     uint8_t *d_img = dp + meta, *img = (uint8_t *)s->hresp.p;
     HIP_TRY(hipMemcpyAsync(dp, hp, meta, hipMemcpyHostToDevice, st));
-    r = pmc_gzip_decompress_batch(ctx, (const uint8_t *)s->heap.p, (uint64_t *)dev(h_soff), (uint32_t *)dev(h_slen),
-                                  m, d_img, (uint64_t *)dev(h_doff), (uint32_t *)dev(h_dcap), (uint32_t *)dev(h_dlen),
-                                  (int32_t *)dev(h_rc), (uint32_t)max_raw, st);
+    r = pmc_gzip_decompress_batch(ctx, (const uint8_t *)s->heap.p, L.soff.d, L.slen.d, m, d_img, L.doff.d, L.dcap.d,
+                                  L.dlen.d, L.rc.d, (uint32_t)max_raw, st);
     if (r) return r;
-    HIP_TRY(hipMemcpyAsync(h_dlen, dev(h_dlen), al256(m * 4ull) * 2, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(L.dlen_rc.h, L.dlen_rc.d, L.dlen_rc.bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(img, d_img, total, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     for (uint32_t k = 0; k < m; k++) {
         const uint32_t i = pick[k];
-        if (h_rc[k] != PMC_OK || h_dlen[k] != ext[i].raw_len) {
-            rc[i] = h_rc[k] != PMC_OK ? h_rc[k] : PMC_Z_DATA_ERROR;
-            continue;
-        }
+        if ((rc[i] = read_verdict(L.rc.h[k], L.dlen.h[k], ext[i].raw_len)) != PMC_OK) continue;
         const int frame = frame_of(i);
-        uint8_t *p = img + pos[i];
-        if (frame == PMC_FRAME_RESP) {  // "$<len>\r\n" value "\r\n"  (protocol.cpp:466-497)
-            const int nd = hlen[i] - 3;
-            p[0] = '$';
-            uint32_t v = ext[i].raw_len;
-            for (int d = nd; d >= 1; d--) {
-                p[d] = (uint8_t)('0' + v % 10);
-                v /= 10;
-            }
-            p[nd + 1] = '\r';
-            p[nd + 2] = '\n';
-            p[hlen[i] + ext[i].raw_len] = '\r';
-            p[hlen[i] + ext[i].raw_len + 1] = '\n';
-        } else if (frame == PMC_FRAME_CUSTOM) {  // value + MSG_SEPARATOR (protocol.hpp:17)
-            p[ext[i].raw_len] = 0x1F;
-        }
-        resp[i] = p;
-        resp_len[i] = hlen[i] + ext[i].raw_len + tail(frame);
+        frame_write(img + pos[i], frame, ext[i].raw_len);
+        resp[i] = img + pos[i];
+        resp_len[i] = hlen[i] + ext[i].raw_len + frame_tail(frame);
     }
     return PMC_OK;
 }
@@ -365,15 +316,6 @@ PMC_API int pmc_store_get_range_batch(pmc_store *s, const pmc_extent *ext, const
     if (n == 0) return PMC_OK;
     StoreCall call(s, s->get_mu);
     pmc_ctx *ctx = s->ctx;
-    auto digits = [](uint32_t v) {
-        uint32_t d = 1;
-        while (v >= 10) {
-            v /= 10;
-            d++;
-        }
-        return d;
-    };
-    const uint32_t tail = frame == PMC_FRAME_RESP ? 2 : frame == PMC_FRAME_CUSTOM ? 1 : 0;
     // live extents: their clamped ranges and their places in the response image
     std::vector<uint32_t> live, ranged, whole;
     std::vector<uint64_t> pos(n, 0);
@@ -390,18 +332,18 @@ PMC_API int pmc_store_get_range_batch(pmc_store *s, const pmc_extent *ext, const
         const RangeOf r = range_of(ext[i].raw_len, kRangeLog2Max, range_off[i], range_len[i]);
         ro[i] = r.o;
         rl[i] = r.L;
-        hlen[i] = (uint8_t)(frame == PMC_FRAME_RESP ? 1 + digits(r.L) + 2 : 0);
+        hlen[i] = (uint8_t)frame_head(frame, r.L);
         pos[i] = total;
-        total += hlen[i] + (uint64_t)r.L + tail;
+        total += hlen[i] + (uint64_t)r.L + frame_tail(frame);
         rc[i] = PMC_OK;
         live.push_back(i);
         // (an empty range needs no device work; a value of <= 4096 bytes cannot carry an index)
         if (r.L) (ext[i].raw_len > (1u << kIdxLog2Min) ? ranged : whole).push_back(i);
     }
     if (live.empty()) return PMC_OK;
-    // device staging: soff | doff (u64) | slen | roff | rlen | dcap | dlen | rc (u32) | response image
+    // device staging: RangeGetStage's arrays | response image
     const uint32_t m = (uint32_t)ranged.size();
-    const uint64_t a8 = al256(m * 8ull), a4 = al256(m * 4ull), meta = a8 * 2 + a4 * 6;
+    const uint64_t meta = RangeGetStage(m).meta;
     int r = s->ghost.ensure(meta + 64);
     if (!r) r = s->gdev.ensure(meta + total + 64);
     if (!r) r = s->hresp.ensure(total + 64);
@@ -410,92 +352,68 @@ PMC_API int pmc_store_get_range_batch(pmc_store *s, const pmc_extent *ext, const
     uint8_t *d_img = (uint8_t *)s->gdev.p + meta, *img = (uint8_t *)s->hresp.p;
     if (m) {
         uint8_t *hp = (uint8_t *)s->ghost.p, *dp = (uint8_t *)s->gdev.p;
-        uint64_t *h_soff = (uint64_t *)hp, *h_doff = (uint64_t *)(hp + a8);
-        uint32_t *h_slen = (uint32_t *)(hp + a8 * 2), *h_roff = (uint32_t *)(hp + a8 * 2 + a4);
-        uint32_t *h_rlen = (uint32_t *)(hp + a8 * 2 + a4 * 2), *h_dcap = (uint32_t *)(hp + a8 * 2 + a4 * 3);
-        uint32_t *h_dlen = (uint32_t *)(hp + a8 * 2 + a4 * 4);
-        int32_t *h_rc = (int32_t *)(hp + a8 * 2 + a4 * 5);
-        const uint64_t d_base = (uint64_t)(dp - hp);
-        auto dev = [&](void *h) { return (uint8_t *)h + d_base; };
+        const RangeGetStage L(m, hp, dp);
         for (uint32_t k = 0; k < m; k++) {
             const uint32_t i = ranged[k];
-            h_soff[k] = ext[i].off;
-            h_slen[k] = ext[i].len;
-            h_roff[k] = ro[i];
-            h_rlen[k] = rl[i];
-            h_doff[k] = pos[i] + hlen[i];
-            h_dcap[k] = rl[i];
+            L.soff.h[k] = ext[i].off;
+            L.slen.h[k] = ext[i].len;
+            L.roff.h[k] = ro[i];
+            L.rlen.h[k] = rl[i];
+            L.doff.h[k] = pos[i] + hlen[i];
+            L.dcap.h[k] = rl[i];
         }
         HIP_TRY(hipMemcpyAsync(dp, hp, meta, hipMemcpyHostToDevice, st));
-        r = pmc_gzip_decompress_range_batch(ctx, (const uint8_t *)s->heap.p, (uint64_t *)dev(h_soff), (uint32_t *)dev(h_slen),
-                                            (uint32_t *)dev(h_roff), (uint32_t *)dev(h_rlen), m, d_img,
-                                            (uint64_t *)dev(h_doff), (uint32_t *)dev(h_dcap), (uint32_t *)dev(h_dlen),
-                                            (int32_t *)dev(h_rc), st);
+        r = pmc_gzip_decompress_range_batch(ctx, (const uint8_t *)s->heap.p, L.soff.d, L.slen.d, L.roff.d, L.rlen.d, m,
+                                            d_img, L.doff.d, L.dcap.d, L.dlen.d, L.rc.d, st);
         if (r) return r;
-        HIP_TRY(hipMemcpyAsync(h_dlen, dev(h_dlen), a4 * 2, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(L.dlen_rc.h, L.dlen_rc.d, L.dlen_rc.bytes, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         for (uint32_t k = 0; k < m; k++) {
             const uint32_t i = ranged[k];
-            if (h_rc[k] == PMC_E_NO_INDEX) whole.push_back(i);
-            else if (h_rc[k] != PMC_OK || h_dlen[k] != rl[i]) rc[i] = h_rc[k] != PMC_OK ? h_rc[k] : PMC_Z_DATA_ERROR;
+            if (L.rc.h[k] == PMC_E_NO_INDEX) whole.push_back(i);
+            else rc[i] = read_verdict(L.rc.h[k], L.dlen.h[k], rl[i]);
         }
     }
-    // the whole reads: extents while their values fit the budget, and the first one always
+    // the whole reads, in rounds over `whole`: the small extents in batch order, then the declined ones
+    std::vector<uint32_t> raw(whole.size());
+    for (size_t w = 0; w < whole.size(); w++) raw[w] = ext[whole[w]].raw_len;
     for (size_t w0 = 0; w0 < whole.size();) {
-        size_t w1 = w0;
-        uint64_t bytes = 0, max_raw = 1;
-        while (w1 < whole.size()) {
-            const uint64_t need = ((uint64_t)ext[whole[w1]].raw_len + 15) & ~(uint64_t)15;
-            if (w1 > w0 && bytes + need > kRangeFallbackBudget) break;
-            bytes += need;
-            max_raw = std::max<uint64_t>(max_raw, ext[whole[w1]].raw_len);
-            w1++;
-        }
-        const uint32_t q = (uint32_t)(w1 - w0);
-        // round staging: soff | doff | cut (slice source) | poff (u64) | slen | dcap | dlen | rc | clen (u32) | values
-        const uint64_t b8 = al256(q * 8ull), b4 = al256(q * 4ull), rmeta = b8 * 4 + b4 * 5;
+        const FallbackRound R = cut_round(raw.data(), raw.size(), w0, kRangeFallbackBudget);
+        const uint32_t q = (uint32_t)(R.end - w0);
+        // round staging: RangeGetRound's arrays | values
+        const uint64_t rmeta = RangeGetRound(q).meta;
         r = s->rhost.ensure(rmeta);
-        if (!r) r = s->rdev.ensure(rmeta + bytes + 64);
+        if (!r) r = s->rdev.ensure(rmeta + R.bytes + 64);
         if (r) return r;
         uint8_t *hp = (uint8_t *)s->rhost.p, *dp = (uint8_t *)s->rdev.p;
-        uint64_t *h_soff = (uint64_t *)hp, *h_doff = (uint64_t *)(hp + b8), *h_cut = (uint64_t *)(hp + b8 * 2);
-        uint64_t *h_poff = (uint64_t *)(hp + b8 * 3);
-        uint32_t *h_slen = (uint32_t *)(hp + b8 * 4), *h_dcap = (uint32_t *)(hp + b8 * 4 + b4);
-        uint32_t *h_dlen = (uint32_t *)(hp + b8 * 4 + b4 * 2);
-        int32_t *h_rc = (int32_t *)(hp + b8 * 4 + b4 * 3);
-        uint32_t *h_clen = (uint32_t *)(hp + b8 * 4 + b4 * 4);
-        const uint64_t d_base = (uint64_t)(dp - hp);
-        auto dev = [&](void *h) { return (uint8_t *)h + d_base; };
+        const RangeGetRound L(q, hp, dp);
         uint64_t at = 0;
         for (uint32_t k = 0; k < q; k++) {
             const uint32_t i = whole[w0 + k];
-            h_soff[k] = ext[i].off;
-            h_slen[k] = ext[i].len;
-            h_doff[k] = at;
-            h_dcap[k] = ext[i].raw_len;
-            h_cut[k] = at + ro[i];
-            h_clen[k] = rl[i];
-            h_poff[k] = pos[i] + hlen[i];
-            at += ((uint64_t)ext[i].raw_len + 15) & ~(uint64_t)15;
+            L.soff.h[k] = ext[i].off;
+            L.slen.h[k] = ext[i].len;
+            L.doff.h[k] = at;
+            L.dcap.h[k] = ext[i].raw_len;
+            L.cut.h[k] = at + ro[i];
+            L.clen.h[k] = rl[i];
+            L.poff.h[k] = pos[i] + hlen[i];
+            at += round16(ext[i].raw_len);
         }
         uint8_t *d_vals = dp + rmeta;
         HIP_TRY(hipMemcpyAsync(dp, hp, rmeta, hipMemcpyHostToDevice, st));
-        r = pmc_gzip_decompress_batch(ctx, (const uint8_t *)s->heap.p, (uint64_t *)dev(h_soff), (uint32_t *)dev(h_slen), q,
-                                      d_vals, (uint64_t *)dev(h_doff), (uint32_t *)dev(h_dcap), (uint32_t *)dev(h_dlen),
-                                      (int32_t *)dev(h_rc), (uint32_t)max_raw, st);
+        r = pmc_gzip_decompress_batch(ctx, (const uint8_t *)s->heap.p, L.soff.d, L.slen.d, q, d_vals, L.doff.d, L.dcap.d,
+                                      L.dlen.d, L.rc.d, (uint32_t)R.max_raw, st);
         if (r) return r;
         // the slices of the values that decoded (rc 0) into their places in the image
-        hipLaunchKernelGGL(compact_kernel, dim3(std::min<uint32_t>((q + 3) / 4, 8192)), dim3(256), 0, st,
-                           (const uint8_t *)d_vals, (const uint64_t *)dev(h_cut), (const uint32_t *)dev(h_clen),
-                           (const int32_t *)dev(h_rc), (const uint64_t *)dev(h_poff), q, d_img);
+        launch_compact(st, q, d_vals, L.cut.d, L.clen.d, L.rc.d, L.poff.d, d_img);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h_dlen, dev(h_dlen), b4 * 2, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(L.dlen_rc.h, L.dlen_rc.d, L.dlen_rc.bytes, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         for (uint32_t k = 0; k < q; k++) {
             const uint32_t i = whole[w0 + k];
-            if (h_rc[k] != PMC_OK || h_dlen[k] != ext[i].raw_len) rc[i] = h_rc[k] != PMC_OK ? h_rc[k] : PMC_Z_DATA_ERROR;
+            rc[i] = read_verdict(L.rc.h[k], L.dlen.h[k], ext[i].raw_len);
         }
-        w0 = w1;
+        w0 = R.end;
     }
     if (total) {
         HIP_TRY(hipMemcpyAsync(img, d_img, total, hipMemcpyDeviceToHost, st));
@@ -503,24 +421,9 @@ PMC_API int pmc_store_get_range_batch(pmc_store *s, const pmc_extent *ext, const
     }
     for (uint32_t i : live) {
         if (rc[i] != PMC_OK) continue;
-        uint8_t *p = img + pos[i];
-        if (frame == PMC_FRAME_RESP) { // "$<len>\r\n" range bytes "\r\n"
-            const int nd = hlen[i] - 3;
-            p[0] = '$';
-            uint32_t v = rl[i];
-            for (int d = nd; d >= 1; d--) {
-                p[d] = (uint8_t)('0' + v % 10);
-                v /= 10;
-            }
-            p[nd + 1] = '\r';
-            p[nd + 2] = '\n';
-            p[hlen[i] + rl[i]] = '\r';
-            p[hlen[i] + rl[i] + 1] = '\n';
-        } else if (frame == PMC_FRAME_CUSTOM) {
-            p[rl[i]] = 0x1F;
-        }
-        resp[i] = p;
-        resp_len[i] = hlen[i] + rl[i] + tail;
+        frame_write(img + pos[i], frame, rl[i]);
+        resp[i] = img + pos[i];
+        resp_len[i] = hlen[i] + rl[i] + frame_tail(frame);
     }
     return PMC_OK;
 }
@@ -556,172 +459,116 @@ PMC_API int pmc_store_set_range_batch(pmc_store *s, pmc_extent *ext, const uint8
         for (uint32_t k = 0; k < m; k++) rc[pick[k]] = code;
         return code;
     };
-    // put staging: soff | poff | doff | noff (u64) | slen | plen | roff | dcap | dlen | rc (u32) | patches | slots
-    const uint64_t a8 = al256(m * 8ull), a4 = al256(m * 4ull), meta = a8 * 4 + a4 * 6;
+    // put staging: RangeSetStage's arrays | patches | member slots (device only)
+    const uint64_t meta = RangeSetStage(m).meta;
     uint64_t pbytes = 0, slots = 0;
     for (uint32_t k = 0; k < m; k++) {
         pbytes += src_len[pick[k]];
-        slots += (gzip_bound(ext[pick[k]].raw_len) + 15) & ~(uint64_t)15;
+        slots += round16(gzip_bound(ext[pick[k]].raw_len));
     }
     const uint64_t pb = al256(pbytes + 16);
     int r = s->phost.ensure(meta + pb);
     if (!r) r = s->pdev.ensure(meta + pb + slots + 64);
     if (r) return fail_all(r);
     uint8_t *hp = (uint8_t *)s->phost.p, *dp = (uint8_t *)s->pdev.p;
-    uint64_t *h_soff = (uint64_t *)hp, *h_poff = (uint64_t *)(hp + a8), *h_doff = (uint64_t *)(hp + a8 * 2);
-    uint64_t *h_noff = (uint64_t *)(hp + a8 * 3);
-    uint32_t *h_slen = (uint32_t *)(hp + a8 * 4), *h_plen = (uint32_t *)(hp + a8 * 4 + a4);
-    uint32_t *h_roff = (uint32_t *)(hp + a8 * 4 + a4 * 2), *h_dcap = (uint32_t *)(hp + a8 * 4 + a4 * 3);
-    uint32_t *h_dlen = (uint32_t *)(hp + a8 * 4 + a4 * 4);
-    int32_t *h_rc = (int32_t *)(hp + a8 * 4 + a4 * 5);
+    const RangeSetStage L(m, hp, dp);
     uint8_t *h_patch = hp + meta, *d_patch = dp + meta, *d_slots = dp + meta + pb;
-    const uint64_t d_base = (uint64_t)(dp - hp);
-    auto dev = [&](void *h) { return (uint8_t *)h + d_base; };
     uint64_t po = 0, doff = 0;
     for (uint32_t k = 0; k < m; k++) {
         const uint32_t i = pick[k];
-        h_soff[k] = ext[i].off;
-        h_slen[k] = ext[i].len;
-        h_poff[k] = po;
-        h_plen[k] = src_len[i];
-        h_roff[k] = range_off[i];
+        L.soff.h[k] = ext[i].off;
+        L.slen.h[k] = ext[i].len;
+        L.poff.h[k] = po;
+        L.plen.h[k] = src_len[i];
+        L.roff.h[k] = range_off[i];
         memcpy(h_patch + po, src + src_off[i], src_len[i]);
         po += src_len[i];
-        h_doff[k] = doff;
-        h_dcap[k] = (uint32_t)gzip_bound(ext[i].raw_len);
-        doff += (gzip_bound(ext[i].raw_len) + 15) & ~(uint64_t)15;
-        h_dlen[k] = 0;
-        h_rc[k] = k < mc ? PMC_OK : PMC_E_NO_INDEX; // (the small ones take the full path)
+        L.doff.h[k] = doff;
+        L.dcap.h[k] = (uint32_t)gzip_bound(ext[i].raw_len);
+        doff += round16(gzip_bound(ext[i].raw_len));
+        L.dlen.h[k] = 0;
+        L.rc.h[k] = k < mc ? PMC_OK : PMC_E_NO_INDEX; // (the small ones take the full path)
     }
     hipStream_t st = ctx->stream;
-    auto ok = [](hipError_t e) {
-        if (e != hipSuccess) set_err("pmc_store_set_range_batch", e);
-        return e == hipSuccess;
-    };
+    const HipOk ok{"pmc_store_set_range_batch"};
     if (!ok(hipMemcpyAsync(dp, hp, meta + pbytes, hipMemcpyHostToDevice, st))) return fail_all(PMC_E_NO_DEVICE);
     // 1. the chunk path
     if (mc) {
-        r = pmc_gzip_rewrite_range_batch(ctx, (const uint8_t *)s->heap.p, (uint64_t *)dev(h_soff), (uint32_t *)dev(h_slen),
-                                         d_patch, (uint64_t *)dev(h_poff), (uint32_t *)dev(h_plen),
-                                         (uint32_t *)dev(h_roff), mc, d_slots, (uint64_t *)dev(h_doff),
-                                         (uint32_t *)dev(h_dcap), (uint32_t *)dev(h_dlen), (int32_t *)dev(h_rc), st);
+        r = pmc_gzip_rewrite_range_batch(ctx, (const uint8_t *)s->heap.p, L.soff.d, L.slen.d, d_patch, L.poff.d, L.plen.d,
+                                         L.roff.d, mc, d_slots, L.doff.d, L.dcap.d, L.dlen.d, L.rc.d, st);
         if (r) return fail_all(r);
-        if (!ok(hipMemcpyAsync(h_dlen, dev(h_dlen), mc * 4ull, hipMemcpyDeviceToHost, st)) ||
-            !ok(hipMemcpyAsync(h_rc, dev(h_rc), mc * 4ull, hipMemcpyDeviceToHost, st)) || !ok(hipStreamSynchronize(st)))
+        if (!ok(hipMemcpyAsync(L.dlen.h, L.dlen.d, mc * 4ull, hipMemcpyDeviceToHost, st)) ||
+            !ok(hipMemcpyAsync(L.rc.h, L.rc.d, mc * 4ull, hipMemcpyDeviceToHost, st)) || !ok(hipStreamSynchronize(st)))
             return fail_all(PMC_E_NO_DEVICE);
     }
+    std::vector<uint32_t> raw;
     for (uint32_t k = 0; k < m; k++)
-        if (h_rc[k] == PMC_E_NO_INDEX) full.push_back(k);
-    // 2. the full path: extents while their values fit the budget, and the first one always
-    for (size_t w0 = 0; w0 < full.size();) {
-        size_t w1 = w0;
-        uint64_t bytes = 0, max_raw = 1;
-        while (w1 < full.size()) {
-            const uint64_t need = ((uint64_t)ext[pick[full[w1]]].raw_len + 15) & ~(uint64_t)15;
-            if (w1 > w0 && bytes + need > kRangeFallbackBudget) break;
-            bytes += need;
-            max_raw = std::max<uint64_t>(max_raw, ext[pick[full[w1]]].raw_len);
-            w1++;
+        if (L.rc.h[k] == PMC_E_NO_INDEX) {
+            full.push_back(k);
+            raw.push_back(ext[pick[k]].raw_len);
         }
-        const uint32_t q = (uint32_t)(w1 - w0);
-        // round staging: soff | voff | cut | poff | doff (u64) | slen | vcap | vlen | vrc | plen | dcap | dlen | rc (u32) |
-        // values
-        const uint64_t b8 = al256(q * 8ull), b4 = al256(q * 4ull), rmeta = b8 * 5 + b4 * 8;
+    // 2. the full path, in rounds over `full`
+    for (size_t w0 = 0; w0 < full.size();) {
+        const FallbackRound R = cut_round(raw.data(), raw.size(), w0, kRangeFallbackBudget);
+        const uint32_t q = (uint32_t)(R.end - w0);
+        // round staging: RangeSetRound's arrays | values
+        const uint64_t rmeta = RangeSetRound(q).meta;
         r = s->rhost.ensure(rmeta);
-        if (!r) r = s->rdev.ensure(rmeta + bytes + 64);
+        if (!r) r = s->rdev.ensure(rmeta + R.bytes + 64);
         if (r) return fail_all(r);
         uint8_t *rh = (uint8_t *)s->rhost.p, *rd = (uint8_t *)s->rdev.p;
-        uint64_t *g_soff = (uint64_t *)rh, *g_voff = (uint64_t *)(rh + b8), *g_cut = (uint64_t *)(rh + b8 * 2);
-        uint64_t *g_poff = (uint64_t *)(rh + b8 * 3), *g_doff = (uint64_t *)(rh + b8 * 4);
-        uint32_t *g_slen = (uint32_t *)(rh + b8 * 5), *g_vcap = (uint32_t *)(rh + b8 * 5 + b4);
-        uint32_t *g_vlen = (uint32_t *)(rh + b8 * 5 + b4 * 2);
-        int32_t *g_vrc = (int32_t *)(rh + b8 * 5 + b4 * 3);
-        uint32_t *g_plen = (uint32_t *)(rh + b8 * 5 + b4 * 4), *g_dcap = (uint32_t *)(rh + b8 * 5 + b4 * 5);
-        uint32_t *g_dlen = (uint32_t *)(rh + b8 * 5 + b4 * 6);
-        int32_t *g_rc = (int32_t *)(rh + b8 * 5 + b4 * 7);
-        const uint64_t r_base = (uint64_t)(rd - rh);
-        auto rdev = [&](void *h) { return (uint8_t *)h + r_base; };
+        const RangeSetRound G(q, rh, rd);
         uint64_t at = 0;
         for (uint32_t j = 0; j < q; j++) {
             const uint32_t k = full[w0 + j], i = pick[k];
-            g_soff[j] = ext[i].off;
-            g_slen[j] = ext[i].len;
-            g_voff[j] = at;
-            g_vcap[j] = ext[i].raw_len;
-            g_cut[j] = at + range_off[i];
-            g_poff[j] = h_poff[k];
-            g_plen[j] = src_len[i];
-            g_doff[j] = h_doff[k];
-            g_dcap[j] = h_dcap[k];
-            at += ((uint64_t)ext[i].raw_len + 15) & ~(uint64_t)15;
+            G.soff.h[j] = ext[i].off;
+            G.slen.h[j] = ext[i].len;
+            G.voff.h[j] = at;
+            G.vcap.h[j] = ext[i].raw_len;
+            G.cut.h[j] = at + range_off[i];
+            G.poff.h[j] = L.poff.h[k];
+            G.plen.h[j] = src_len[i];
+            G.doff.h[j] = L.doff.h[k];
+            G.dcap.h[j] = L.dcap.h[k];
+            at += round16(ext[i].raw_len);
         }
         uint8_t *d_vals = rd + rmeta;
         if (!ok(hipMemcpyAsync(rd, rh, rmeta, hipMemcpyHostToDevice, st))) return fail_all(PMC_E_NO_DEVICE);
-        r = pmc_gzip_decompress_batch(ctx, (const uint8_t *)s->heap.p, (uint64_t *)rdev(g_soff), (uint32_t *)rdev(g_slen), q,
-                                      d_vals, (uint64_t *)rdev(g_voff), (uint32_t *)rdev(g_vcap), (uint32_t *)rdev(g_vlen),
-                                      (int32_t *)rdev(g_vrc), (uint32_t)max_raw, st);
+        r = pmc_gzip_decompress_batch(ctx, (const uint8_t *)s->heap.p, G.soff.d, G.slen.d, q, d_vals, G.voff.d, G.vcap.d,
+                                      G.vlen.d, G.vrc.d, (uint32_t)R.max_raw, st);
         if (r) return fail_all(r);
         // the patches over the values that decoded (rc 0), then the values compressed into their slots
-        hipLaunchKernelGGL(compact_kernel, dim3(std::min<uint32_t>((q + 3) / 4, 8192)), dim3(256), 0, st,
-                           (const uint8_t *)d_patch, (const uint64_t *)rdev(g_poff), (const uint32_t *)rdev(g_plen),
-                           (const int32_t *)rdev(g_vrc), (const uint64_t *)rdev(g_cut), q, d_vals);
+        launch_compact(st, q, d_patch, G.poff.d, G.plen.d, G.vrc.d, G.cut.d, d_vals);
         if (!ok(hipGetLastError())) return fail_all(PMC_E_NO_DEVICE);
-        r = pmc_gzip_compress_batch(ctx, d_vals, (uint64_t *)rdev(g_voff), (uint32_t *)rdev(g_vcap), q, d_slots,
-                                    (uint64_t *)rdev(g_doff), (uint32_t *)rdev(g_dcap), (uint32_t *)rdev(g_dlen),
-                                    (int32_t *)rdev(g_rc), (uint32_t)max_raw, st);
+        r = pmc_gzip_compress_batch(ctx, d_vals, G.voff.d, G.vcap.d, q, d_slots, G.doff.d, G.dcap.d, G.dlen.d, G.rc.d,
+                                    (uint32_t)R.max_raw, st);
         if (r) return fail_all(r);
-        if (!ok(hipMemcpyAsync(g_vlen, rdev(g_vlen), b4 * 2, hipMemcpyDeviceToHost, st)) ||
-            !ok(hipMemcpyAsync(g_dlen, rdev(g_dlen), b4 * 2, hipMemcpyDeviceToHost, st)) || !ok(hipStreamSynchronize(st)))
+        if (!ok(hipMemcpyAsync(G.vlen_vrc.h, G.vlen_vrc.d, G.vlen_vrc.bytes, hipMemcpyDeviceToHost, st)) ||
+            !ok(hipMemcpyAsync(G.dlen_rc.h, G.dlen_rc.d, G.dlen_rc.bytes, hipMemcpyDeviceToHost, st)) ||
+            !ok(hipStreamSynchronize(st)))
             return fail_all(PMC_E_NO_DEVICE);
         for (uint32_t j = 0; j < q; j++) {
             const uint32_t k = full[w0 + j], i = pick[k];
-            if (g_vrc[j] != PMC_OK || g_vlen[j] != ext[i].raw_len) h_rc[k] = g_vrc[j] != PMC_OK ? g_vrc[j] : PMC_Z_DATA_ERROR;
-            else h_rc[k] = g_rc[j];
-            h_dlen[k] = g_dlen[j];
+            const int32_t v = read_verdict(G.vrc.h[j], G.vlen.h[j], ext[i].raw_len);
+            L.rc.h[k] = v != PMC_OK ? v : G.rc.h[j];
+            L.dlen.h[k] = G.dlen.h[j];
         }
-        w0 = w1;
+        w0 = R.end;
     }
-    // 3. new extents by member length (the old ones stay until the members are in)
+    // 3. new extents by member length, the members from the slots into them; only then are the old ones released
+    // (a value that got no new extent, or whose new extent was lost to a failed compact, keeps its old one)
     std::vector<pmc_extent> fresh(m, pmc_extent{0, 0, 0, 0, 0});
-    {
-        std::lock_guard<std::mutex> a(s->alloc_mu);
-        for (uint32_t k = 0; k < m; k++) {
-            const uint32_t i = pick[k];
-            h_noff[k] = 0;
-            if (h_rc[k] != PMC_OK) {
-                rc[i] = h_rc[k];
-                continue;
-            }
-            const uint32_t size = extent_size(h_dlen[k]);
-            uint64_t off = 0;
-            if (!store_alloc(s, size, &off)) {
-                rc[i] = h_rc[k] = PMC_Z_MEM_ERROR; // the compact pass skips it
-                continue;
-            }
-            fresh[k] = pmc_extent{off, size, h_dlen[k], ext[i].raw_len, 1};
-            h_noff[k] = off;
-        }
-    }
-    // 4. members from the slots into the new extents
-    bool moved = ok(hipMemcpyAsync(dev(h_noff), h_noff, m * 8ull, hipMemcpyHostToDevice, st)) &&
-                 ok(hipMemcpyAsync(dev(h_rc), h_rc, m * 4ull, hipMemcpyHostToDevice, st)) &&
-                 ok(hipMemcpyAsync(dev(h_dlen), h_dlen, m * 4ull, hipMemcpyHostToDevice, st));
-    if (moved) {
-        hipLaunchKernelGGL(compact_kernel, dim3(std::min<uint32_t>((m + 3) / 4, 8192)), dim3(256), 0, st,
-                           (const uint8_t *)d_slots, (const uint64_t *)dev(h_doff), (const uint32_t *)dev(h_dlen),
-                           (const int32_t *)dev(h_rc), (const uint64_t *)dev(h_noff), m, (uint8_t *)s->heap.p);
-        moved = ok(hipGetLastError()) && ok(hipStreamSynchronize(st));
-    }
+    const bool moved = store_commit(
+        s, ok, st, m, d_slots, L.doff, L.dlen, L.rc, L.noff, true, [&](uint32_t k) -> pmc_extent & { return fresh[k]; },
+        [&](uint32_t k) { return ext[pick[k]].raw_len; });
     std::lock_guard<std::mutex> a(s->alloc_mu);
     for (uint32_t k = 0; k < m; k++) {
         const uint32_t i = pick[k];
-        if (!(fresh[k].flags & 1)) continue;
-        if (!moved) { // the new extents hold nothing: the old ones stay
-            store_release(s, fresh[k]);
-            rc[i] = PMC_E_NO_DEVICE;
+        if (L.rc.h[k] != PMC_OK) {
+            rc[i] = L.rc.h[k];
             continue;
         }
-        store_release(s, ext[i]);
+        s->alloc.release(ext[i]);
         ext[i] = fresh[k];
     }
     return moved ? PMC_OK : PMC_E_NO_DEVICE;
@@ -734,43 +581,37 @@ PMC_API int pmc_store_read_members(pmc_store *s, const pmc_extent *ext, uint32_t
     StoreCall call(s, s->get_mu);
     for (uint32_t i = 0; i < n; i++)
         if (!(ext[i].flags & 1)) return PMC_E_ARG;
-    // gather the members on the device (compact_kernel), then one D2H
-    const uint64_t meta = al256(n * 8ull) * 2 + al256(n * 4ull) * 2;
+    // gather the members on the device (compact_kernel), then one D2H.  staging: MembersStage's arrays | members
+    const uint64_t meta = MembersStage(n).meta;
     uint64_t total = 0;
     for (uint32_t i = 0; i < n; i++) total += ext[i].len;
     int r = s->ghost.ensure(meta + total + 64);
     if (!r) r = s->gdev.ensure(meta + total + 64);
     if (r) return r;
     uint8_t *hp = (uint8_t *)s->ghost.p, *dp = (uint8_t *)s->gdev.p;
-    uint64_t *h_soff = (uint64_t *)hp, *h_poff = (uint64_t *)(hp + al256(n * 8ull));
-    uint32_t *h_len = (uint32_t *)(hp + al256(n * 8ull) * 2);
-    int32_t *h_rc = (int32_t *)((uint8_t *)h_len + al256(n * 4ull));
-    const uint64_t d_base = (uint64_t)(dp - hp);
-    auto dev = [&](void *h) { return (uint8_t *)h + d_base; };
+    const MembersStage L(n, hp, dp);
     uint64_t p = 0;
     for (uint32_t i = 0; i < n; i++) {
-        h_soff[i] = ext[i].off;
-        h_poff[i] = p;
-        h_len[i] = ext[i].len;
-        h_rc[i] = 0;
+        L.soff.h[i] = ext[i].off;
+        L.poff.h[i] = p;
+        L.len.h[i] = ext[i].len;
+        L.rc.h[i] = 0;
         p += ext[i].len;
     }
     hipStream_t st = s->gst;
     HIP_TRY(hipMemcpyAsync(dp, hp, meta, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(compact_kernel, dim3(std::min<uint32_t>((n + 3) / 4, 8192)), dim3(256), 0, st,
-                       (const uint8_t *)s->heap.p, (const uint64_t *)dev(h_soff), (const uint32_t *)dev(h_len),
-                       (const int32_t *)dev(h_rc), (const uint64_t *)dev(h_poff), n, dp + meta);
+    launch_compact(st, n, (const uint8_t *)s->heap.p, L.soff.d, L.len.d, L.rc.d, L.poff.d, dp + meta);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(hp + meta, dp + meta, total, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    for (uint32_t i = 0; i < n; i++) memcpy(dst + dst_off[i], hp + meta + h_poff[i], ext[i].len);
+    for (uint32_t i = 0; i < n; i++) memcpy(dst + dst_off[i], hp + meta + L.poff.h[i], ext[i].len);
     return PMC_OK;
 }
 
 PMC_API int pmc_store_free(pmc_store *s, pmc_extent *ext, uint32_t n) {
     if (!s || (n && !ext)) return PMC_E_ARG;
     std::lock_guard<std::mutex> lock(s->alloc_mu);
-    for (uint32_t i = 0; i < n; i++) store_release(s, ext[i]);
+    for (uint32_t i = 0; i < n; i++) s->alloc.release(ext[i]);
     return PMC_OK;
 }
 
@@ -779,9 +620,9 @@ PMC_API uint8_t *pmc_store_data(pmc_store *s) { return s ? (uint8_t *)s->heap.p 
 PMC_API int pmc_store_stats(pmc_store *s, uint64_t *used, uint64_t *reserved, uint64_t *heap) {
     if (!s) return PMC_E_ARG;
     std::lock_guard<std::mutex> lock(s->alloc_mu);
-    if (used) *used = s->used;
-    if (reserved) *reserved = s->bump;
-    if (heap) *heap = s->heap_bytes;
+    if (used) *used = s->alloc.used;
+    if (reserved) *reserved = s->alloc.bump;
+    if (heap) *heap = s->alloc.heap_bytes;
     return PMC_OK;
 }
 

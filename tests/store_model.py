@@ -1,5 +1,6 @@
-"""A plain model of the device store's host allocator (csrc/pmc_store.hip) and the churn script that the
-store tests follow (tests/test_store_model.py on the CPU, tests/test_gpu_store_churn.py on the device).
+"""A plain model of the device store's host allocator (csrc/pmc_store_plan.hpp StoreHeap) and the churn script
+that the store tests follow (tests/test_store_model.py and, through StoreHeap itself, tests/test_host_store.py on
+the CPU, tests/test_gpu_store_churn.py on the device).
 
 The allocator, as the header comment of pmc_store.hip and the store paragraph of include/pmc_codec.h state it:
 an extent reserves cap = the member's length rounded up to 16 bytes; a cap above 8192 is rounded up again to a
