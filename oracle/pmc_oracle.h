@@ -61,6 +61,22 @@ typedef struct {
 } oracle_stats;
 void oracle_get_stats(oracle_stats *s);
 
+/* Block facts: what trees.c computes on the way to each block of the last oracle_gzip_compress or
+ * oracle_gzip_compress_dp call.  Index 0 is the literal/length tree, 1 the distance tree, 2 the bit-length
+ * tree.  leaves: symbols of non-zero frequency before build_tree forces a code (leaves[0] is the heap a
+ * lane of the trees kernel must hold); overflow: gen_bitlen's count of nodes cut to max_length;
+ * depth_ties: pqdownheap comparisons of two entries of equal frequency and unequal depth (the ones
+ * `smaller` decides by depth); opt_len and static_len in bits as _tr_flush_block compares them (tree
+ * header included), stored_len in bytes; type 0 stored, 1 fixed, 2 dynamic; symbols: literals + matches.
+ * Returns the number of blocks of that call and writes the first min(cap, blocks, 64) of them. */
+typedef struct {
+    uint32_t leaves[3], overflow[3], depth_ties[3];
+    int32_t max_code[3], max_blindex;
+    uint32_t type, symbols;
+    uint64_t opt_len, static_len, stored_len;
+} oracle_block_facts;
+size_t oracle_get_block_facts(oracle_block_facts *out, size_t cap);
+
 /* splitmix64-based synthetic value generator shared with the GPU generator
  * (SURVEY.md §8d): value i of size V is corpus[off_i : off_i+V],
  * off_i = splitmix64(seed ^ i) mod (corpus_len - V + 1). kind 1 = random [A-Za-z0-9]. */

@@ -111,6 +111,25 @@ def last_stats():
     return {k: getattr(s, k) for k, _ in s._fields_}
 
 
+class _BlockFacts(ctypes.Structure):
+    _fields_ = [("leaves", ctypes.c_uint32 * 3), ("overflow", ctypes.c_uint32 * 3), ("depth_ties", ctypes.c_uint32 * 3),
+                ("max_code", ctypes.c_int32 * 3), ("max_blindex", ctypes.c_int32),
+                ("type", ctypes.c_uint32), ("symbols", ctypes.c_uint32),
+                ("opt_len", ctypes.c_uint64), ("static_len", ctypes.c_uint64), ("stored_len", ctypes.c_uint64)]
+
+
+def last_block_facts():
+    """The facts of every block of the last compress() (pmc_oracle.h: oracle_block_facts), one dict per block;
+    the per-tree fields are (lit/len, distance, bit-length) tuples.  At most 64 blocks are kept."""
+    L = lib()
+    L.oracle_get_block_facts.restype = ctypes.c_size_t
+    L.oracle_get_block_facts.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
+    buf = (_BlockFacts * 64)()
+    n = L.oracle_get_block_facts(buf, 64)
+    return [{k: (tuple(getattr(b, k)) if k in ("leaves", "overflow", "depth_ties", "max_code") else int(getattr(b, k)))
+             for k, _ in _BlockFacts._fields_} for b in buf[:min(n, 64)]]
+
+
 def gen_values(corpus: bytes, seed: int, kind: int, first: int, n: int, vlen: int) -> np.ndarray:
     out = np.empty((n, vlen), dtype=np.uint8)
     lib().oracle_gen_values(corpus, len(corpus), seed, kind, first, n, vlen,

@@ -10,6 +10,22 @@
  * gets the longer code. */
 #include <string.h>
 #include "oracle_internal.h"
+#include "pmc_oracle.h"
+
+/* Block facts (oracle_get_block_facts): what the functions below compute on the way, kept per block of the
+ * last compress.  Written beside the arithmetic, never read by it: no output byte depends on them. */
+#define FACTS_KEPT 64
+static oracle_block_facts g_facts[FACTS_KEPT];
+static size_t g_nfacts;
+static oracle_block_facts g_cur; /* the block being flushed */
+static int g_tree;               /* which tree build_tree is on: 0 lit/len, 1 distance, 2 bit-length */
+
+size_t oracle_get_block_facts(oracle_block_facts *out, size_t cap) {
+    size_t n = g_nfacts < FACTS_KEPT ? g_nfacts : FACTS_KEPT;
+    if (n > cap) n = cap;
+    if (n) memcpy(out, g_facts, n * sizeof(*out));
+    return g_nfacts;
+}
 
 static const int extra_lbits[LENGTH_CODES] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2,
                                               2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
@@ -125,6 +141,7 @@ static void init_block(tstate *s) {
 void tr_init(tstate *s, uint8_t *out) {
     tr_static_init();
     memset(s, 0, sizeof(*s));
+    g_nfacts = 0;
     s->l_desc.dyn_tree = s->dyn_ltree;
     s->l_desc.stat_desc = &static_l_desc;
     s->d_desc.dyn_tree = s->dyn_dtree;
@@ -143,7 +160,12 @@ static void pqdownheap(tstate *s, ct_data *tree, int k) {
     int v = s->heap[k];
     int j = k << 1;
     while (j <= s->heap_len) {
+        /* (facts: comparisons that the depth decides -- equal frequency, unequal depth) */
+        if (j < s->heap_len && tree[s->heap[j + 1]].Freq == tree[s->heap[j]].Freq &&
+            s->depth[s->heap[j + 1]] != s->depth[s->heap[j]])
+            g_cur.depth_ties[g_tree]++;
         if (j < s->heap_len && smaller(tree, s->heap[j + 1], s->heap[j], s->depth)) j++;
+        if (tree[v].Freq == tree[s->heap[j]].Freq && s->depth[v] != s->depth[s->heap[j]]) g_cur.depth_ties[g_tree]++;
         if (smaller(tree, v, s->heap[j], s->depth)) break;
         s->heap[k] = s->heap[j];
         k = j;
@@ -178,6 +200,7 @@ static void gen_bitlen(tstate *s, tree_desc *desc) {
         s->opt_len += (uint64_t)f * (unsigned)(bits + xbits);
         if (stree) s->static_len += (uint64_t)f * (unsigned)(stree[n].Len + xbits);
     }
+    g_cur.overflow[g_tree] = (uint32_t)overflow;
     if (overflow == 0) return;
     do {
         bits = max_length - 1;
@@ -217,6 +240,7 @@ static void build_tree(tstate *s, tree_desc *desc) {
             tree[n].Len = 0;
         }
     }
+    g_cur.leaves[g_tree] = (uint32_t)s->heap_len; /* before the forced codes */
     while (s->heap_len < 2) {
         node = s->heap[++(s->heap_len)] = (max_code < 2 ? ++max_code : 0);
         tree[node].Freq = 1;
@@ -225,6 +249,7 @@ static void build_tree(tstate *s, tree_desc *desc) {
         if (stree) s->static_len -= stree[node].Len;
     }
     desc->max_code = max_code;
+    g_cur.max_code[g_tree] = max_code;
     for (n = s->heap_len / 2; n >= 1; n--) pqdownheap(s, tree, n);
     node = elems;
     do {
@@ -311,6 +336,7 @@ static int build_bl_tree(tstate *s) {
     int max_blindex;
     scan_tree(s, s->dyn_ltree, s->l_desc.max_code);
     scan_tree(s, s->dyn_dtree, s->d_desc.max_code);
+    g_tree = 2;
     build_tree(s, &s->bl_desc);
     for (max_blindex = BL_CODES - 1; max_blindex >= 3; max_blindex--)
         if (s->bl_tree[bl_order[max_blindex]].Len != 0) break;
@@ -373,25 +399,36 @@ static void tr_stored_block(tstate *s, const uint8_t *buf, uint64_t stored_len, 
 void tr_flush_block(tstate *s, const uint8_t *buf, uint64_t stored_len, int last) {
     uint64_t opt_lenb, static_lenb;
     int max_blindex;
+    memset(&g_cur, 0, sizeof(g_cur));
+    g_cur.symbols = s->last_lit;
+    g_tree = 0;
     build_tree(s, &s->l_desc);
+    g_tree = 1;
     build_tree(s, &s->d_desc);
     max_blindex = build_bl_tree(s);
+    g_cur.max_blindex = max_blindex;
+    g_cur.opt_len = s->opt_len, g_cur.static_len = s->static_len, g_cur.stored_len = stored_len;
+    g_cur.type = 2;
     opt_lenb = (s->opt_len + 3 + 7) >> 3;
     static_lenb = (s->static_len + 3 + 7) >> 3;
     if (static_lenb <= opt_lenb) opt_lenb = static_lenb;
     if (stored_len + 4 <= opt_lenb && buf != 0) {
         tr_stored_block(s, buf, stored_len, last);
         s->n_stored++;
+        g_cur.type = 0;
     } else if (static_lenb == opt_lenb) {
         send_bits(s, (1 << 1) + last, 3);
         compress_block(s, static_ltree, static_dtree);
         s->n_fixed++;
+        g_cur.type = 1;
     } else {
         send_bits(s, (2 << 1) + last, 3);
         send_all_trees(s, s->l_desc.max_code + 1, s->d_desc.max_code + 1, max_blindex + 1);
         compress_block(s, s->dyn_ltree, s->dyn_dtree);
         s->n_dynamic++;
     }
+    if (g_nfacts < FACTS_KEPT) g_facts[g_nfacts] = g_cur;
+    g_nfacts++;
     init_block(s);
     if (last) bi_windup(s);
 }

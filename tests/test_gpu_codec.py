@@ -258,9 +258,12 @@ def test_ragged_batch_in_the_packed_sort_class_vs_oracle(ctx, D, golden, cap):
 
 
 def test_skewed_histograms_vs_oracle(ctx, D):
-    """Fibonacci-weighted symbol streams: deep Huffman trees (zlib's gen_bitlen length-limit
-    fix-up for the 15-bit and 7-bit trees), wide alphabets (the trees pass's large-heap
-    path) and everything between, byte-exact against the oracle."""
+    """Fibonacci-weighted symbol streams, byte-exact against the oracle.  By the oracle's block facts
+    (oracle_block_facts), of the 30 values 22 are dynamic blocks and 8 stored ones, which show nothing
+    of the trees; 3 overflow the 7-bit bit-length tree (zlib's gen_bitlen
+    length-limit fix-up), none the 15-bit literal/length tree -- matches flatten the skew -- and none the
+    distance tree; 14 use more literal/length symbols than the trees pass's first heap holds (its large-heap
+    path).  The arms this leaves out are tests/test_gpu_trees.py's."""
     from oracle import pyoracle as O
     rng = np.random.default_rng(11)
     fib = [1, 1]
