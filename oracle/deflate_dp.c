@@ -43,30 +43,103 @@ static unsigned lcp_capped(const dp_ctx *c, size_t i, size_t q, unsigned cap) {
     return l;
 }
 
+/* Rule variants (oracle_compress_variant): 0 is zlib's rule set, the only one the two compressors use. */
+static int g_rule;
+static unsigned g_arg;
+
+/* Search log of the last oracle_gzip_compress_dp call (values of at most ORACLE_LOG_MAX bytes). */
+static oracle_search_rec g_slog[ORACLE_LOG_MAX];
+static oracle_token_rec g_tlog[ORACLE_LOG_MAX];
+static size_t g_nslog, g_ntlog;
+static int g_log_on;
+
+size_t oracle_get_search_log(oracle_search_rec *out, size_t cap) {
+    size_t n = g_nslog < cap ? g_nslog : cap;
+    if (out && n) memcpy(out, g_slog, n * sizeof *out);
+    return g_nslog;
+}
+size_t oracle_get_token_log(oracle_token_rec *out, size_t cap) {
+    size_t n = g_ntlog < cap ? g_ntlog : cap;
+    if (out && n) memcpy(out, g_tlog, n * sizeof *out);
+    return g_ntlog;
+}
+static void log_token(size_t pos, unsigned len, unsigned dist) {
+    if (g_log_on && g_ntlog < ORACLE_LOG_MAX) {
+        oracle_token_rec *t = &g_tlog[g_ntlog++];
+        t->pos = (uint32_t)pos, t->len = len, t->dist = dist;
+    }
+}
+
+/* The chain of every position of a value, as the sort sees it: cnt[p] = earlier positions of p's hash
+ * (position 0, which zlib cannot tell from NIL, not counted), for p <= len - 3.  Returns len - 2 (0 below 3). */
+size_t oracle_chain_counts(const uint8_t *in, size_t len, uint32_t *cnt, size_t cap) {
+    size_t npos = len >= MIN_MATCH ? len - (MIN_MATCH - 1) : 0;
+    uint32_t *seen = (uint32_t *)calloc(HASH_SIZE, sizeof(uint32_t));
+    for (size_t p = 0; p < npos && p < cap; p++) {
+        unsigned h = ((in[p] << 10) ^ (in[p + 1] << 5) ^ in[p + 2]) & HASH_MASK;
+        cnt[p] = seen[h];
+        if (p) seen[h]++;
+    }
+    free(seen);
+    return npos;
+}
+
 /* Search result for position i: returns the best length (> b0) or 0 if none beats b0. */
 static unsigned dp_search(const dp_ctx *c, size_t i, unsigned b0, size_t B, size_t *qbest) {
     unsigned C = b0 >= GOOD_LENGTH ? MAX_CHAIN >> 2 : MAX_CHAIN;
     size_t rk = c->rank[i];
     unsigned nice = (unsigned)((c->len - i) < NICE_LENGTH ? (c->len - i) : NICE_LENGTH);
-    unsigned best = 0, nexam = 0;
+    unsigned left = nice; /* bytes a match may hold */
+    unsigned best = 0, nexam = 0, ncap = 0, best_ord = 0, first_len = 0, collide = 0, end = ORACLE_END_START;
+    if (g_rule == ORACLE_RULE_CHAIN_NOCAP) C = 0xFFFFFFFFu;
+    if (g_rule == ORACLE_RULE_CAP4096_OFF && C == MAX_CHAIN) C = 0xFFFFFFFFu;
+    if (g_rule == ORACLE_RULE_GOOD_OFF) C = MAX_CHAIN;
+    if (g_rule == ORACLE_RULE_GOOD_33) C = b0 >= GOOD_LENGTH + 1 ? MAX_CHAIN >> 2 : MAX_CHAIN;
+    if (g_rule == ORACLE_RULE_NICE_258) nice = NICE_LENGTH;
     for (size_t k = rk; k-- > 0;) {
         size_t q = c->S[k];
-        if (c->h[q] != c->h[i]) break;
+        if (c->h[q] != c->h[i]) { end = ORACLE_END_HASH; break; }
         size_t d = i - q;
-        if (q <= B) break;
-        if (nexam == 0 ? d > MAX_DIST : d >= MAX_DIST) break;
+        if (g_rule == ORACLE_RULE_NIL_OK ? q < B : q <= B) { end = ORACLE_END_NIL; break; }
+        if (nexam == 0 ? d > MAX_DIST : d >= MAX_DIST) { end = ORACLE_END_DIST; break; }
+        if (g_rule == ORACLE_RULE_FIRST_K && nexam >= g_arg) { end = ORACLE_END_HASH; break; }
         nexam++;
-        unsigned l = lcp_capped(c, i, q, nice);
-        if (l > best) { /* strictly longer: nearest wins ties */
-            best = l;
-            *qbest = q;
-            if (l >= nice) break;
-        }
-        if (nexam == C) break;
+        if (!(g_rule == ORACLE_RULE_SKIP_K && nexam - 1 == g_arg)) {
+            unsigned l = lcp_capped(c, i, q, left);
+            if (g_rule == ORACLE_RULE_NICE_258 && l == left) /* the compare runs on: zeros lie past the value */
+                while (l < NICE_LENGTH && q + l < c->len && c->b[q + l] == 0) l++;
+            if (nexam == 1) first_len = l;
+            if (l < MIN_MATCH) collide = 1;
+            if (!(g_rule == ORACLE_RULE_COLLIDE_FREE && l < MIN_MATCH)) ncap++;
+            if (g_rule == ORACLE_RULE_TIE_FAR ? l >= best : l > best) { /* strictly longer: nearest wins ties */
+                best = l;
+                best_ord = nexam - 1;
+                *qbest = q;
+                if (l >= nice) { end = ORACLE_END_NICE; break; }
+            }
+        } else
+            ncap++;
+        if (ncap == C) { end = C != MAX_CHAIN >> 2 ? ORACLE_END_CAP4096 : ORACLE_END_CAP1024; break; }
     }
+    if (best > left) best = left;
     g_stats.searches++;
     g_stats.candidates += nexam;
+    if (g_log_on && g_nslog < ORACLE_LOG_MAX) {
+        oracle_search_rec *r = &g_slog[g_nslog++];
+        r->pos = (uint32_t)i, r->prev_length = b0, r->examined = nexam, r->end = end, r->collide = collide;
+        r->first_len = first_len;
+        r->win_ord = best ? best_ord : 0xFFFFFFFFu;
+        r->win_len = best, r->win_dist = best ? (uint32_t)(i - *qbest) : 0;
+    }
+    if (g_rule == ORACLE_RULE_LAZY_GE) return best >= b0 && best >= MIN_MATCH ? best : 0;
     return best > b0 ? best : 0;
+}
+
+size_t oracle_compress_variant(int rule, unsigned arg, const uint8_t *in, size_t len, uint8_t *out) {
+    g_rule = rule, g_arg = arg;
+    size_t n = oracle_gzip_compress_dp(in, len, out);
+    g_rule = 0, g_arg = 0;
+    return n;
 }
 
 size_t oracle_gzip_compress_dp(const uint8_t *in, size_t len, uint8_t *out) {
@@ -79,6 +152,8 @@ size_t oracle_gzip_compress_dp(const uint8_t *in, size_t len, uint8_t *out) {
     size_t p, n;
     memset(&g_stats, 0, sizeof(g_stats));
     g_stats.positions = len;
+    g_log_on = len <= ORACLE_LOG_MAX;
+    g_nslog = g_ntlog = 0;
 
     /* stage 1+2: hashes and a stable counting sort by hash */
     for (p = 0; p < npos; p++) {
@@ -124,11 +199,14 @@ size_t oracle_gzip_compress_dp(const uint8_t *in, size_t len, uint8_t *out) {
             if (m) {
                 match_length = m;
                 match_start = (unsigned)q;
-                if (m == MIN_MATCH && i - q > TOO_FAR) match_length = MIN_MATCH - 1;
+                size_t far = g_rule == ORACLE_RULE_TOO_FAR_GE ? TOO_FAR - 1 : g_rule == ORACLE_RULE_TOO_FAR_4097 ? TOO_FAR + 1 : TOO_FAR;
+                if (m == MIN_MATCH && i - q > far) match_length = MIN_MATCH - 1;
             }
         }
-        if (prev_length >= MIN_MATCH && match_length <= prev_length) {
+        if (prev_length >= MIN_MATCH &&
+            (g_rule == ORACLE_RULE_LAZY_LT || g_rule == ORACLE_RULE_LAZY_GE ? match_length < prev_length : match_length <= prev_length)) {
             bflush = tr_tally_dist(t, (unsigned)(i - 1 - prev_match), prev_length - MIN_MATCH);
+            log_token(i - 1, prev_length, (unsigned)(i - 1 - prev_match));
             g_stats.matches++;
             i += prev_length - 1;
             match_available = 0;
@@ -136,6 +214,7 @@ size_t oracle_gzip_compress_dp(const uint8_t *in, size_t len, uint8_t *out) {
             if (bflush) FLUSH(i, 0);
         } else if (match_available) {
             bflush = tr_tally_lit(t, in[i - 1]);
+            log_token(i - 1, 0, in[i - 1]);
             g_stats.literals++;
             if (bflush) FLUSH(i, 0);
             i++;
@@ -146,6 +225,7 @@ size_t oracle_gzip_compress_dp(const uint8_t *in, size_t len, uint8_t *out) {
     }
     if (match_available) {
         tr_tally_lit(t, in[i - 1]);
+        log_token(i - 1, 0, in[i - 1]);
         g_stats.literals++;
     }
     FLUSH(i, 1);

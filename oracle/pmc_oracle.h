@@ -77,6 +77,52 @@ typedef struct {
 } oracle_block_facts;
 size_t oracle_get_block_facts(oracle_block_facts *out, size_t cap);
 
+/* Search log: what the last oracle_gzip_compress_dp call (a value of at most ORACLE_LOG_MAX bytes; longer values
+ * leave an empty log) did, for tests/front_values.py.  One oracle_search_rec per longest_match call of the lazy
+ * parse: the position, prev_length, the candidates examined, the winner (the longest candidate, nearest first:
+ * win_ord is its 0-based place in the chain, 0xFFFFFFFF with no candidate; win_len may be <= prev_length, in which
+ * case the parse ignores it), first_len the nearest candidate's common prefix (capped at nice), how the walk
+ * ended, and whether a candidate of the same hash and other leading bytes was examined.  One oracle_token_rec per
+ * symbol: len 0 is a literal whose byte is dist.  Both return the number of records of the call and write the
+ * first min(cap, records). */
+#define ORACLE_LOG_MAX 65536
+enum { ORACLE_END_HASH = 0,  /* the entry below the chain has another hash */
+       ORACLE_END_START,     /* the chain reached the start of the sorted array */
+       ORACLE_END_NIL,       /* ... position 0 (or the window base), which zlib reads as NIL */
+       ORACLE_END_CAP4096, ORACLE_END_CAP1024, ORACLE_END_NICE, ORACLE_END_DIST };
+typedef struct {
+    uint32_t pos, prev_length, examined, win_ord, win_len, win_dist, first_len, end, collide;
+} oracle_search_rec;
+typedef struct { uint32_t pos, len, dist; } oracle_token_rec;
+size_t oracle_get_search_log(oracle_search_rec *out, size_t cap);
+size_t oracle_get_token_log(oracle_token_rec *out, size_t cap);
+/* cnt[p], p <= len - 3: the earlier positions of p's hash, position 0 left out.  Returns len - 2. */
+size_t oracle_chain_counts(const uint8_t *in, size_t len, uint32_t *cnt, size_t cap);
+
+/* The dp encoder with exactly one rule altered (never a default; tests define "this value decides rule X" as
+ * "the variant's member differs"):
+ *   TOO_FAR_GE    a length-3 match is dropped from distance 4096 (zlib: from 4097)
+ *   TOO_FAR_4097  ... from 4098
+ *   CHAIN_NOCAP   no candidate cap
+ *   CAP4096_OFF   no cap of 4096 (the 1024 of prev_length >= 32 stays)
+ *   GOOD_OFF      cap 4096 even when prev_length >= 32
+ *   GOOD_33       cap 1024 only from prev_length >= 33
+ *   TIE_FAR       the farthest candidate of equal length wins
+ *   NIL_OK        position 0 is a candidate
+ *   LAZY_LT       the pending match is emitted only if match_length < prev_length
+ *   LAZY_GE       a match as long as the pending one replaces it (longest_match may return prev_length, and the
+ *                 pending match is emitted only if match_length < prev_length): LAZY_LT alone changes nothing,
+ *                 because longest_match returns a length above prev_length or none
+ *   COLLIDE_FREE  candidates whose three bytes differ do not count towards the cap
+ *   FIRST_K       candidates from ordinal arg on are ignored
+ *   SKIP_K        exactly the candidate of ordinal arg is ignored (it still counts towards the cap)
+ *   NICE_258      nice stays 258 near the end of the value: the compare runs on into the zeros past it, the
+ *                 winner is picked by that length and the result clipped to the bytes left */
+enum { ORACLE_RULE_ZLIB = 0, ORACLE_RULE_TOO_FAR_GE, ORACLE_RULE_TOO_FAR_4097, ORACLE_RULE_CHAIN_NOCAP,
+       ORACLE_RULE_GOOD_OFF, ORACLE_RULE_GOOD_33, ORACLE_RULE_TIE_FAR, ORACLE_RULE_NIL_OK, ORACLE_RULE_LAZY_LT,
+       ORACLE_RULE_COLLIDE_FREE, ORACLE_RULE_FIRST_K, ORACLE_RULE_SKIP_K, ORACLE_RULE_NICE_258, ORACLE_RULE_CAP4096_OFF, ORACLE_RULE_LAZY_GE };
+size_t oracle_compress_variant(int rule, unsigned arg, const uint8_t *in, size_t len, uint8_t *out);
+
 /* splitmix64-based synthetic value generator shared with the GPU generator
  * (SURVEY.md §8d): value i of size V is corpus[off_i : off_i+V],
  * off_i = splitmix64(seed ^ i) mod (corpus_len - V + 1). kind 1 = random [A-Za-z0-9]. */

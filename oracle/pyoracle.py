@@ -130,6 +130,54 @@ def last_block_facts():
              for k, _ in _BlockFacts._fields_} for b in buf[:min(n, 64)]]
 
 
+# ---- search facts and rule variants (pmc_oracle.h) -----------------------------------------------------------
+LOG_MAX = 65536
+END_HASH, END_START, END_NIL, END_CAP4096, END_CAP1024, END_NICE, END_DIST = range(7)
+SEARCH_DTYPE = np.dtype([(k, "<u4") for k in ("pos", "prev_length", "examined", "win_ord", "win_len", "win_dist",
+                                               "first_len", "end", "collide")])
+TOKEN_DTYPE = np.dtype([(k, "<u4") for k in ("pos", "len", "dist")])
+RULES = {name: k + 1 for k, name in enumerate((
+    "too_far_ge", "too_far_4097", "chain_nocap", "good_off", "good_33", "tie_far", "nil_ok", "lazy_lt",
+    "collide_free", "first_k", "skip_k", "nice_258", "cap4096_off", "lazy_ge"))}
+
+
+def _log(fn, dtype):
+    fn.restype = ctypes.c_size_t
+    fn.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
+    n = fn(None, 0)
+    out = np.zeros(n, dtype)
+    if n:
+        fn(out.ctypes.data_as(ctypes.c_void_p), n)
+    return out
+
+
+def last_search_log():
+    """(searches, tokens) of the last compress(dp=True), as structured arrays (SEARCH_DTYPE, TOKEN_DTYPE); empty
+    for a value above LOG_MAX bytes."""
+    L = lib()
+    return _log(L.oracle_get_search_log, SEARCH_DTYPE), _log(L.oracle_get_token_log, TOKEN_DTYPE)
+
+
+def chain_counts(data: bytes) -> np.ndarray:
+    """The earlier positions of each position's hash (position 0 left out), for positions 0 .. len - 3."""
+    L = lib()
+    L.oracle_chain_counts.restype = ctypes.c_size_t
+    L.oracle_chain_counts.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
+    out = np.zeros(max(len(data) - 2, 0), np.uint32)
+    L.oracle_chain_counts(data, len(data), out.ctypes.data_as(ctypes.c_void_p), len(out))
+    return out
+
+
+def compress_variant(rule: str, arg: int, data: bytes) -> bytes:
+    """The dp encoder with one rule altered (RULES); never what a member is checked against."""
+    L = lib()
+    L.oracle_compress_variant.restype = ctypes.c_size_t
+    L.oracle_compress_variant.argtypes = [ctypes.c_int, ctypes.c_uint, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p]
+    out = ctypes.create_string_buffer(L.oracle_gzip_bound(len(data)))
+    n = L.oracle_compress_variant(RULES[rule], arg, data, len(data), out)
+    return out.raw[:n]
+
+
 def gen_values(corpus: bytes, seed: int, kind: int, first: int, n: int, vlen: int) -> np.ndarray:
     out = np.empty((n, vlen), dtype=np.uint8)
     lib().oracle_gen_values(corpus, len(corpus), seed, kind, first, n, vlen,
