@@ -311,13 +311,73 @@ int pmc_ctx_range_verify_counts(pmc_ctx *ctx, uint64_t counts[2]);
  * their request), counts[3] = chunks compressed again and counts[4] = chunks copied verbatim, both for the requests
  * answered PMC_OK (an empty patch copies its K chunks).
  *
- * (pmc_store_set_range_batch, below, is the call that always performs the write.)  Not provided: growth and APPEND
- * (K changes), a host-memory entry point, slab, group and server wrappers, members without chunk CRCs. */
+ * pmc_gzip_grow_range_batch ("growing writes", below) moves the same counters.
+ *
+ * (pmc_store_set_range_batch, below, is the call that always performs the write.)  Not provided here: growth and
+ * APPEND (K changes: "growing writes", below), a host-memory entry point, slab, group and server wrappers, members
+ * without chunk CRCs. */
 int pmc_gzip_rewrite_range_batch(pmc_ctx *ctx, const uint8_t *src, const uint64_t *src_off, const uint32_t *src_len,
                                  const uint8_t *patch, const uint64_t *patch_off, const uint32_t *patch_len,
                                  const uint32_t *range_off, uint32_t n, uint8_t *dst, const uint64_t *dst_off,
                                  const uint32_t *dst_cap, uint32_t *dst_len, int32_t *rc, void *stream);
 int pmc_ctx_rewrite_counts(pmc_ctx *ctx, uint64_t counts[5]);
+
+/* ---- growing writes ----------------------------------------------------------------------------
+ * A ranged write that may make the value longer: Redis APPEND (range_off = S) and SETRANGE past the end (zero
+ * padding between the old end and the patch).  Chunks 0 .. K-2 of the old member are non-last chunks, and a
+ * non-last chunk's span depends on its own bytes only -- neither the value's length nor the chunk's place enters
+ * it -- so they keep their spans.  The old last chunk is made again (it stops being the last: it loses BFINAL and
+ * gains the empty stored block), the chunks behind it are new, the trailer is folded from the entries, and the
+ * header is written for the new number of chunks.  The same kernels as "ranged writes", which keep the old
+ * member's (S, K) for what they read apart from the new value's (S', K') for what they write.
+ *
+ * pmc_gzip_grow_range_batch has pmc_gzip_rewrite_range_batch's signature, streams, locks, compress-direction
+ * scratch, one synchronous read-back and rounds.  It is a superset: a request with range_off + patch_len <= S is
+ * answered exactly as pmc_gzip_rewrite_range_batch answers it -- verdict, bytes and counters -- but for the empty
+ * patch of step 2.  (pmc_gzip_rewrite_range_batch keeps refusing growth with PMC_E_ARG.)  Per request, in this
+ * order:
+ *   1. Member check.  The rewrite's step 1 on the old member with its own S and K, the fold of the K entries
+ *      against the trailer with the old chunk lengths included.  Failure: PMC_E_NO_INDEX.
+ *   2. patch_len == 0: the output is the input member, WHATEVER range_off IS (subject to the capacity rule) --
+ *      SETRANGE with an empty value does not pad.  This differs from the rewrite call, where an empty patch at
+ *      range_off > S is PMC_E_ARG.
+ *   3. Bounds.  end = (uint64) range_off + patch_len.  end <= S: the rewrite's steps 4 to 6.  end > 0xFFFFFFFF:
+ *      PMC_E_ARG (ISIZE would wrap).  Otherwise S' = end and K' = ceil(S' / C); K' > 8190: PMC_E_NO_INDEX (a
+ *      fresh compress of V' would carry no chunk CRCs; the caller's full path writes that form), nothing decoded.
+ *   4. New value V' of S' bytes: bytes [0, min(range_off, S)) are V's, bytes [S, range_off) are zero (SETRANGE's
+ *      padding; empty for an append), bytes [range_off, S') are the patch.
+ *   5. Touched chunks: a = min(range_off >> 15, K - 1) .. K' - 1, K' - a of them; the old last chunk is always
+ *      among them, because its span changes even where its bytes do not.  Chunk a is an EDGE CHUNK if and only if
+ *      min(range_off, S) > a C (some of its old bytes survive): it is decoded whole by the old geometry (as chunk a
+ *      of K, the last one if a == K - 1) and must pass the ranged read's structural test and its CRC-32 entry, or
+ *      the request is PMC_E_NO_INDEX.  There is never a second edge chunk (no old byte lies behind the patch); no
+ *      other touched chunk is decoded or looked at.
+ *   6. Recompression.  Chunks a .. K' - 1 are emitted as at their place in a value of S' bytes, K' - 1 being the
+ *      last.  A failed lane-order guard: PMC_E_NO_INDEX.
+ *   7. Assembly by "member index" for S' and K': XLEN = 8 K' + 12, K' - 1 offsets and K' entries, the spans of
+ *      chunks 0 .. a - 1 copied from the old member, the fold with the new chunk lengths, ISIZE = S'.  need >
+ *      dst_cap[i]: PMC_E_CAPACITY, dst_len[i] = need, nothing written; pmc_gzip_bound(S') always suffices.
+ * BYTES: if the old member is what pmc_gzip_compress_batch writes for V at PMC_LEVEL_FAST_ALL with the index and
+ * index_crc switches on, then on PMC_OK the new member is byte for byte what that call writes for V' -- whatever
+ * the context's level and switches are at the time of the call.  For a foreign writer's member the rewrite's rule
+ * holds with S' for S.
+ * INTEGRITY: as for the rewrite: the call vouches for the one chunk it decoded and for nothing else, and does not
+ * launder damage -- a damaged untouched chunk still fails the new member's full read, a damaged entry fails the
+ * fold of step 1.  It answers PMC_OK, PMC_E_NO_INDEX, PMC_E_ARG or PMC_E_CAPACITY.
+ * WRITES: whatever the outcome, no byte outside [dst_off[i], dst_off[i] + need) of the requests with rc PMC_OK is
+ * written.  Offsets may be unaligned; requests are independent.
+ * n == 0 returns PMC_OK; a NULL context or (n > 0) a NULL array returns PMC_E_ARG without touching a device.
+ * Scratch: the rewrite's rule, unchanged -- a request touches at most 8190 chunks, so it fits a round of 8192
+ * (csrc/pmc_plan.hpp plan_patch, plan_patch_round).
+ * pmc_ctx_rewrite_counts counts these calls too: counts[2] = edge chunks decoded, and for a served growing request
+ * counts[3] += K' - a, counts[4] += a.
+ *
+ * (pmc_store_grow_range_batch and pmc_store_append_batch, below, always perform the write.)  Not provided:
+ * shrinking, slab, group and server wrappers, a host-memory entry point, a shortcut for all-zero chunks. */
+int pmc_gzip_grow_range_batch(pmc_ctx *ctx, const uint8_t *src, const uint64_t *src_off, const uint32_t *src_len,
+                              const uint8_t *patch, const uint64_t *patch_off, const uint32_t *patch_len,
+                              const uint32_t *range_off, uint32_t n, uint8_t *dst, const uint64_t *dst_off,
+                              const uint32_t *dst_cap, uint32_t *dst_len, int32_t *rc, void *stream);
 
 /* ---- preset dictionary ----------------------------------------------------------------------
  * A context holds at most one dictionary of 1 .. PMC_DICT_MAX bytes (host memory at the call, copied
@@ -575,6 +635,19 @@ int pmc_store_get_range_batch(pmc_store *s, const pmc_extent *ext, const uint32_
  * is the new extent, raw_len unchanged. */
 int pmc_store_set_range_batch(pmc_store *s, pmc_extent *ext, const uint8_t *src, const uint64_t *src_off,
                               const uint32_t *src_len, const uint32_t *range_off, uint32_t n, int32_t *rc);
+/* pmc_store_set_range_batch with growth ("growing writes", above): the value becomes S' = max(raw_len, range_off +
+ * src_len) bytes, zeros in [raw_len, range_off).  Everything else is that call's: locks, distinct extents, old and
+ * new extents briefly coexisting, ext[i] unchanged and live on any failure.  Extents of raw_len > 32768 go through
+ * pmc_gzip_grow_range_batch into slots of pmc_gzip_bound(S'); what it declines and the smaller extents are read
+ * whole, CRC-checked, laid into a zeroed scratch value of S' bytes, patched and compressed at the context's current
+ * level and switches (a 30 KB value that grows past 32 KiB thereby becomes indexed), in rounds of at most 64 MiB
+ * over S'.  PMC_E_ARG: an empty or freed extent, duplicates, S' > 536870912 (the server's MAX_REQUEST_SIZE, Redis's
+ * own limit for both commands).  An empty patch is PMC_OK and changes nothing, whatever range_off is.  On success
+ * ext[i].raw_len = S'.  pmc_store_append_batch is the same with range_off[i] = ext[i].raw_len. */
+int pmc_store_grow_range_batch(pmc_store *s, pmc_extent *ext, const uint8_t *src, const uint64_t *src_off,
+                               const uint32_t *src_len, const uint32_t *range_off, uint32_t n, int32_t *rc);
+int pmc_store_append_batch(pmc_store *s, pmc_extent *ext, const uint8_t *src, const uint64_t *src_off,
+                           const uint32_t *src_len, uint32_t n, int32_t *rc);
 /* Copy extents' compressed bytes (gzip members) to host memory: member i at dst + dst_off[i]. */
 int pmc_store_read_members(pmc_store *s, const pmc_extent *ext, uint32_t n, uint8_t *dst,
                            const uint64_t *dst_off);

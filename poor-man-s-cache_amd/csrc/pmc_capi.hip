@@ -1559,7 +1559,7 @@ PMC_API int pmc_ctx_range_verify_counts(pmc_ctx *ctx, uint64_t counts[2]) {
     return PMC_OK;
 }
 
-// ---- ranged writes (pmc_deflate_patch.hip; include/pmc_codec.h "ranged writes") ----------------------------
+// ---- ranged and growing writes (pmc_deflate_patch.hip; include/pmc_codec.h "ranged writes") ----------------
 // plan_patch (pmc_plan.hpp) -> scan, prefix sum, the total read back; then rounds of whole requests, each of at
 // most kPatchRoundChunks touched chunks (PMC_PATCH_ROUND_CHUNKS lowers that, for tests): tables, edge decode,
 // overlay, the fast parse, emit, finish, copy.  A round's kernels are only enqueued.
@@ -1704,11 +1704,12 @@ static int rewrite_batch_body(pmc_ctx *ctx, PatchArgs P, hipStream_t st) {
     return PMC_OK;
 }
 
-PMC_API int pmc_gzip_rewrite_range_batch(pmc_ctx *ctx, const uint8_t *src, const uint64_t *src_off,
-                                         const uint32_t *src_len, const uint8_t *patch, const uint64_t *patch_off,
-                                         const uint32_t *patch_len, const uint32_t *range_off, uint32_t n, uint8_t *dst,
-                                         const uint64_t *dst_off, const uint32_t *dst_cap, uint32_t *dst_len,
-                                         int32_t *rc, void *stream) {
+// the two entry points: the same call, with growth refused by the scan (grow 0) or served (grow 1)
+static int rewrite_range_batch(pmc_ctx *ctx, int grow, const uint8_t *src, const uint64_t *src_off,
+                               const uint32_t *src_len, const uint8_t *patch, const uint64_t *patch_off,
+                               const uint32_t *patch_len, const uint32_t *range_off, uint32_t n, uint8_t *dst,
+                               const uint64_t *dst_off, const uint32_t *dst_cap, uint32_t *dst_len, int32_t *rc,
+                               void *stream) {
     if (!ctx || (n && (!src || !src_off || !src_len || !patch || !patch_off || !patch_len || !range_off || !dst ||
                        !dst_off || !dst_cap || !dst_len || !rc)))
         return PMC_E_ARG;
@@ -1731,9 +1732,28 @@ PMC_API int pmc_gzip_rewrite_range_batch(pmc_ctx *ctx, const uint8_t *src, const
     P.dst_len = dst_len;
     P.rc = rc;
     P.n = n;
+    P.grow = grow;
     r = rewrite_batch_body(ctx, P, st);
     const int r2 = dir_leave(ctx, 0, st);
     return r ? r : r2;
+}
+
+PMC_API int pmc_gzip_rewrite_range_batch(pmc_ctx *ctx, const uint8_t *src, const uint64_t *src_off,
+                                         const uint32_t *src_len, const uint8_t *patch, const uint64_t *patch_off,
+                                         const uint32_t *patch_len, const uint32_t *range_off, uint32_t n, uint8_t *dst,
+                                         const uint64_t *dst_off, const uint32_t *dst_cap, uint32_t *dst_len,
+                                         int32_t *rc, void *stream) {
+    return rewrite_range_batch(ctx, 0, src, src_off, src_len, patch, patch_off, patch_len, range_off, n, dst, dst_off,
+                               dst_cap, dst_len, rc, stream);
+}
+
+PMC_API int pmc_gzip_grow_range_batch(pmc_ctx *ctx, const uint8_t *src, const uint64_t *src_off,
+                                      const uint32_t *src_len, const uint8_t *patch, const uint64_t *patch_off,
+                                      const uint32_t *patch_len, const uint32_t *range_off, uint32_t n, uint8_t *dst,
+                                      const uint64_t *dst_off, const uint32_t *dst_cap, uint32_t *dst_len, int32_t *rc,
+                                      void *stream) {
+    return rewrite_range_batch(ctx, 1, src, src_off, src_len, patch, patch_off, patch_len, range_off, n, dst, dst_off,
+                               dst_cap, dst_len, rc, stream);
 }
 
 PMC_API int pmc_ctx_rewrite_counts(pmc_ctx *ctx, uint64_t counts[5]) {

@@ -1,4 +1,5 @@
-// pmc_deflate_patch.hip -- ranged writes of indexed members (include/pmc_codec.h "ranged writes").
+// pmc_deflate_patch.hip -- ranged and growing writes of indexed members (include/pmc_codec.h "ranged writes",
+// "growing writes").
 //
 // An indexed member with chunk CRCs can be rewritten chunk by chunk: the chunks a patch does not touch keep their
 // compressed spans (they start on the bytes the index names), the touched ones are compressed again alone (a
@@ -21,6 +22,11 @@
 //                         header with every offset and CRC entry, the fold, the trailer, the counters
 //   patch_copy_kernel     one block per (request, chunk): the span from the old member or from the slot to its
 //                         place -- dword stores through alignbyte, plain vector stores only
+// A write may make the value longer (PatchArgs::grow; without it the scan refuses growth).  Two geometries are then
+// kept apart: the old member's (S, K) for everything that is read -- the member check, the untouched spans and
+// entries, the edge decode -- and the new value's (S2, K2) (pmc_plan.hpp grow_of) for everything that is written:
+// the regions, the overlay with its zero gap [S, range_off), the emit's chunk lengths, last chunk and window
+// arithmetic, the header, the fold, the trailer and the copy.  Where the value does not grow the two are the same.
 #include <hip/hip_runtime.h>
 
 #include "pmc_device.hpp"
@@ -55,6 +61,13 @@ __device__ __forceinline__ uint32_t patch_old_end(const uint8_t *m, uint32_t len
 __device__ __forceinline__ uint32_t patch_clen(uint32_t S, uint32_t k) {
     const uint32_t c0 = k << kPatchLg;
     return S - c0 < kIdxChunk ? S - c0 : kIdxChunk;
+}
+// the new value's length for a request the scan took with touched chunks (cnt != 0: the scan has checked the sum)
+__device__ __forceinline__ uint32_t patch_new_size(uint32_t S, uint32_t off, uint32_t len) {
+    return off + len > S ? off + len : S;
+}
+__device__ __forceinline__ uint32_t patch_chunks(uint32_t S) {
+    return (uint32_t)(((uint64_t)S + kIdxChunk - 1) >> kPatchLg);
 }
 // x^(8 clen) mod P: what a chunk of clen bytes shifts the CRC register by (run_lv's recurrence)
 __device__ __forceinline__ uint32_t patch_shift(uint32_t clen) {
@@ -95,6 +108,20 @@ __device__ __forceinline__ void patch_block_copy(uint8_t *dst, const uint8_t *sr
     for (uint64_t j = nw * 4 + t; j < n; j += nt) d[j] = s[j];
 }
 
+// n zero bytes at dst, the same way
+__device__ __forceinline__ void patch_block_zero(uint8_t *dst, uint64_t n, uint32_t t, uint32_t nt) {
+    PMC_GLB uint8_t *d = (PMC_GLB uint8_t *)dst;
+    uint64_t head = (4 - ((uintptr_t)d & 3)) & 3;
+    head = head < n ? head : n;
+    for (uint64_t j = t; j < head; j += nt) d[j] = 0;
+    d += head;
+    n -= head;
+    PMC_GLB uint32_t *dw = (PMC_GLB uint32_t *)d;
+    const uint64_t nw = n >> 2;
+    for (uint64_t j = t; j < nw; j += nt) dw[j] = 0u;
+    for (uint64_t j = nw * 4 + t; j < n; j += nt) d[j] = 0;
+}
+
 __global__ void __launch_bounds__(256) patch_scan_kernel(PatchArgs P) {
     for (uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; v < P.n; v += (uint64_t)gridDim.x * blockDim.x) {
         const uint8_t *m = P.src + P.src_off[v];
@@ -110,13 +137,14 @@ __global__ void __launch_bounds__(256) patch_scan_kernel(PatchArgs P) {
                 crc = multmodp(clen == kIdxChunk ? xc : patch_shift(clen), crc) ^ idx_u32(m + at + 4 * k);
             }
             if (crc == idx_u32(m + len - 8)) {
-                const PatchOf p = patch_of(S, kPatchLg, P.range_off[v], P.patch_len[v]);
-                if (!p.ok) {
+                const GrowOf g = grow_of(S, kPatchLg, P.range_off[v], P.patch_len[v]);
+                // (a rewrite refuses what reaches past the end, an empty patch behind it too)
+                if ((!P.grow && (uint64_t)P.range_off[v] + P.patch_len[v] > S) || g.verdict == kGrowArg) {
                     rc = PMC_E_ARG_DEV;
-                } else { // (until the finish kernel: pending)
+                } else if (g.verdict != kGrowNoIndex) { // (until the finish kernel: pending)
                     rc = kDeflateRetry;
-                    cnt = p.items;
-                    ka = p.a;
+                    cnt = g.items;
+                    ka = g.a;
                 }
             }
         }
@@ -137,7 +165,8 @@ __global__ void __launch_bounds__(256) patch_tables_kernel(PatchArgs P) {
             const uint64_t it = P.pre[v] - P.i0;
             uint32_t rlen = 0;
             if (cnt) {
-                const uint32_t S = idx_u32(P.src + P.src_off[v] + P.src_len[v] - 4);
+                const uint32_t S = patch_new_size(idx_u32(P.src + P.src_off[v] + P.src_len[v] - 4), P.range_off[v],
+                                                  P.patch_len[v]);
                 const uint64_t c0 = (uint64_t)P.ka[v] << kPatchLg, e = c0 + (uint64_t)cnt * kIdxChunk;
                 rlen = (uint32_t)((e < S ? e : S) - c0);
             }
@@ -182,7 +211,9 @@ __global__ void __launch_bounds__(64) patch_decode_kernel(PatchArgs P) {
             const uint8_t *mm = P.src + P.src_off[v];
             const uint32_t len = P.src_len[v];
             const PatchMember M = patch_member(mm, len);
-            const PatchOf p = patch_of(M.S, kPatchLg, P.range_off[v], P.patch_len[v]);
+            // (old geometry throughout: a growing write has edge a only, and the old last chunk is decoded as the
+            // last one, to the trailer)
+            const GrowOf p = grow_of(M.S, kPatchLg, P.range_off[v], P.patch_len[v]);
             if ((it & 1) ? !p.edge_b : !p.edge_a) {
                 st = 3;
             } else {
@@ -229,11 +260,17 @@ __global__ void __launch_bounds__(256) patch_overlay_kernel(PatchArgs P) {
         const uint32_t v = patch_request(P, P.i0 + t);
         const uint32_t k = P.ka[v] + (uint32_t)(P.i0 + t - P.pre[v]);
         const uint32_t S = idx_u32(P.src + P.src_off[v] + P.src_len[v] - 4);
-        const uint64_t c0 = (uint64_t)k << kPatchLg, ce = c0 + patch_clen(S, k);
+        const uint32_t S2 = patch_new_size(S, P.range_off[v], P.patch_len[v]);
+        const uint64_t c0 = (uint64_t)k << kPatchLg, ce = c0 + patch_clen(S2, k);
         const uint64_t o = P.range_off[v], e = o + P.patch_len[v];
-        const uint64_t lo = c0 > o ? c0 : o, hi = ce < e ? ce : e; // the chunk's part of the patch (hi > lo)
-        patch_block_copy(P.stage + t * kIdxChunk + (lo - c0), P.patch + P.patch_off[v] + (lo - o), hi - lo, threadIdx.x,
-                         blockDim.x);
+        // the chunk's part of the gap between the old end and the patch: zeros (the stage is reused scratch, and the
+        // decode of the old last chunk ends at the old end)
+        const uint64_t zlo = c0 > S ? c0 : S, zhi = ce < o ? ce : o;
+        if (zhi > zlo) patch_block_zero(P.stage + t * kIdxChunk + (zlo - c0), zhi - zlo, threadIdx.x, blockDim.x);
+        const uint64_t lo = c0 > o ? c0 : o, hi = ce < e ? ce : e; // the chunk's part of the patch
+        if (hi > lo)
+            patch_block_copy(P.stage + t * kIdxChunk + (lo - c0), P.patch + P.patch_off[v] + (lo - o), hi - lo,
+                             threadIdx.x, blockDim.x);
     }
 }
 
@@ -337,13 +374,15 @@ __global__ void __launch_bounds__(256) patch_emit_kernel(PatchArgs P) {
             const uint32_t k = P.ka[v] + (uint32_t)(P.i0 + t - P.pre[v]);
             const uint8_t *m = P.src + P.src_off[v];
             const PatchMember M = patch_member(m, P.src_len[v]);
-            const uint32_t clen = patch_clen(M.S, k);
+            const uint32_t S2 = patch_new_size(M.S, P.range_off[v], P.patch_len[v]);
+            const uint32_t clen = patch_clen(S2, k);
             W.b = P.stage + t * kIdxChunk;
             W.bw = reinterpret_cast<uint32_t *>(W.b);
             W.outb = P.slots + t * kPatchSlotBytes;
             W.outw = reinterpret_cast<uint32_t *>(W.outb);
             const uint32_t crc = wave_crc32(W.b, clen, crc_tab);
-            span = patch_emit_chunk(W, clen, (uint64_t)k << kPatchLg, M.S, k + 1 == M.K, P, t * kPatchSegs, hist);
+            span = patch_emit_chunk(W, clen, (uint64_t)k << kPatchLg, S2, k + 1 == patch_chunks(S2), P, t * kPatchSegs,
+                                    hist);
             if (l == 0) P.crc[t] = crc;
         }
         if (l == 0) {
@@ -374,31 +413,35 @@ __global__ void __launch_bounds__(256) patch_finish_kernel(PatchArgs P) {
         const uint8_t *m = P.src + P.src_off[v];
         uint8_t *d = P.dst + P.dst_off[v];
         const PatchMember M = patch_member(m, len);
-        uint32_t need = 0;
+        uint32_t need = 0, S2 = M.S, K2 = M.K;
         if (P.fail[v] || P.pfail[v]) {
             rc = PMC_E_NO_INDEX;
         } else if (cnt == 0) { // an empty patch: the member as it is (patch_copy_kernel)
             need = len;
             rc = need > cap ? PMC_E_CAPACITY_DEV : PMC_OK;
         } else {
-            const IdxPlan ix = idx_plan(M.S, kIdxChunk, true);
+            // the new value's S2 bytes in K2 chunks.  An untouched chunk lies before the patch or, where the value
+            // keeps its length, behind it: the old last chunk's span is never carried into a longer value
+            S2 = patch_new_size(M.S, P.range_off[v], P.patch_len[v]);
+            K2 = patch_chunks(S2);
+            const IdxPlan ix = idx_plan(S2, kIdxChunk, true);
             const uint64_t it0 = P.pre[v] - P.i0;
             const uint32_t xc = patch_shift(kIdxChunk);
             // first pass: the spans' sum and the fold of the entries
             uint64_t sum = 0;
             uint32_t crc = 0;
-            for (uint32_t kb = 0; kb < M.K; kb += 64) {
+            for (uint32_t kb = 0; kb < K2; kb += 64) {
                 const uint32_t k = kb + l;
                 uint32_t sp = 0, e = 0;
-                if (k < M.K) {
+                if (k < K2) {
                     const bool touched = k >= ka && k < ka + cnt;
                     sp = touched ? P.span[it0 + (k - ka)] : patch_old_end(m, len, M, k) - patch_old_start(m, M, k);
                     e = touched ? P.crc[it0 + (k - ka)] : idx_u32(m + M.crc_at + 4 * k);
                 }
                 sum += wave_sum_u32(sp);
-                const uint32_t nk = M.K - kb < 64 ? M.K - kb : 64;
+                const uint32_t nk = K2 - kb < 64 ? K2 - kb : 64;
                 for (uint32_t j = 0; j < nk; j++) {
-                    const uint32_t clen = patch_clen(M.S, kb + j);
+                    const uint32_t clen = patch_clen(S2, kb + j);
                     crc = multmodp(clen == kIdxChunk ? xc : patch_shift(clen), crc) ^ readlane(e, (int)j);
                 }
             }
@@ -419,20 +462,20 @@ __global__ void __launch_bounds__(256) patch_finish_kernel(PatchArgs P) {
                     const uint64_t ext = (uint64_t)'P' | (uint64_t)'C' << 8 | (uint64_t)(4 + 4 * ix.K) << 16 | 1ull << 32;
                     d[ix.crc_at - kIdxCrcFixed + (l - 20)] = (uint8_t)(ext >> (8 * (l - 20)));
                 } else if (l < 36) {
-                    const uint32_t x = l < 32 ? crc : M.S;
+                    const uint32_t x = l < 32 ? crc : S2;
                     d[need - 8 + (l - 28)] = (uint8_t)(x >> (8 * (l & 3)));
                 }
                 uint64_t run = ix.hdr;
-                for (uint32_t kb = 0; kb < M.K; kb += 64) {
+                for (uint32_t kb = 0; kb < K2; kb += 64) {
                     const uint32_t k = kb + l;
                     uint32_t sp = 0, e = 0;
-                    if (k < M.K) {
+                    if (k < K2) {
                         const bool touched = k >= ka && k < ka + cnt;
                         sp = touched ? P.span[it0 + (k - ka)] : patch_old_end(m, len, M, k) - patch_old_start(m, M, k);
                         e = touched ? P.crc[it0 + (k - ka)] : idx_u32(m + M.crc_at + 4 * k);
                     }
                     const uint32_t incl = wave_incl_scan_dpp(sp);
-                    if (k < M.K) {
+                    if (k < K2) {
                         if (k) patch_put_u32(d + kIdxHdrFixed + 4 * (k - 1), (uint32_t)(run + incl - sp));
                         patch_put_u32(d + ix.crc_at + 4 * k, e);
                     }
@@ -447,7 +490,7 @@ __global__ void __launch_bounds__(256) patch_finish_kernel(PatchArgs P) {
             declined += rc == PMC_E_NO_INDEX ? 1 : 0;
             if (rc == PMC_OK) {
                 compressed += cnt;
-                copied += M.K - cnt;
+                copied += K2 - cnt;
             }
         }
     }
@@ -471,11 +514,12 @@ __global__ void __launch_bounds__(256) patch_copy_kernel(PatchArgs P) {
             continue;
         }
         const PatchMember M = patch_member(m, len);
-        const uint32_t hdrn = idx_plan(M.S, kIdxChunk, true).hdr;
+        const uint32_t S2 = patch_new_size(M.S, P.range_off[v], P.patch_len[v]);
+        const uint32_t hdrn = idx_plan(S2, kIdxChunk, true).hdr;
         const uint64_t it0 = P.pre[v] - P.i0;
-        for (uint32_t k = blockIdx.y; k < M.K; k += gridDim.y) {
+        for (uint32_t k = blockIdx.y; k < patch_chunks(S2); k += gridDim.y) {
             const bool touched = k >= ka && k < ka + cnt;
-            const uint32_t os = patch_old_start(m, M, k);
+            const uint32_t os = touched ? 0u : patch_old_start(m, M, k); // (the old member has no chunk k >= K)
             const uint8_t *s = touched ? P.slots + (it0 + (k - ka)) * kPatchSlotBytes : m + os;
             const uint32_t nb = touched ? P.span[it0 + (k - ka)] : patch_old_end(m, len, M, k) - os;
             // (the new offsets are in the header the finish kernel wrote)

@@ -307,8 +307,8 @@ __global__ void inflate_range_scan_kernel(InflateArgs a, RangeArgs R);
 template <bool kVerify>
 __global__ void inflate_range_kernel(InflateArgs a, RangeArgs R);
 __global__ void inflate_range_finish_kernel(InflateArgs a, RangeArgs R);
-// ranged writes of indexed members (pmc_deflate_patch.hip; include/pmc_codec.h "ranged writes"): the request
-// rows (pmc_plan.hpp PatchPlan) and one round's chunk rows (PatchRound)
+// ranged and growing writes of indexed members (pmc_deflate_patch.hip; include/pmc_codec.h "ranged writes",
+// "growing writes"): the request rows (pmc_plan.hpp PatchPlan) and one round's chunk rows (PatchRound)
 struct PatchArgs {
     const uint8_t *src;       // old members
     const uint64_t *src_off;
@@ -323,7 +323,10 @@ struct PatchArgs {
     int32_t *rc;
     uint32_t n;
     int32_t off;              // the fast parse or the chunk decoder is not available: every request is declined
-    uint32_t *cnt;            // [n] touched chunks, 0 = answered by the scan or an empty patch
+    // pmc_gzip_grow_range_batch: a patch may reach past the value's end (pmc_plan.hpp grow_of); else the scan
+    // answers such a request PMC_E_ARG
+    int32_t grow;
+    uint32_t *cnt;           // [n] touched chunks, 0 = answered by the scan or an empty patch
     uint32_t *ka;             // [n] the first touched chunk
     uint32_t *fail;           // [n] an edge chunk did not decode as its index and CRC entry say, or an emit failed
     const uint64_t *pre;      // [n] exclusive prefix sum of cnt: the request's first chunk item

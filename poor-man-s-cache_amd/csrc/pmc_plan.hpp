@@ -524,6 +524,54 @@ PMC_HD inline PatchOf patch_of(uint32_t isize, uint32_t lg, uint32_t off, uint32
     return p;
 }
 
+// The same for a write that may make the value longer (include/pmc_codec.h "growing writes"): the patch's bytes
+// become [off, off + len) of a value of S2 = max(isize, off + len) bytes in K2 chunks, with zeros in [isize, off).
+// verdict: kGrowServe -- touched chunks a .. a + items - 1; kGrowSame -- an empty patch, the member as it is,
+// whatever off is; kGrowArg -- S2 would not fit ISIZE; kGrowNoIndex -- K2 chunks are more than a member with chunk
+// CRCs may have.  Within the value (off + len <= isize) everything is patch_of's.  A growing write touches every
+// chunk from a = min(off >> lg, K - 1) on, the old last chunk always (it stops being the last); chunk a is its
+// only edge chunk, and is one where some of its old bytes survive: min(off, isize) > a 2^lg.
+enum : uint32_t { kGrowServe = 0, kGrowSame = 1, kGrowArg = 2, kGrowNoIndex = 3 };
+struct GrowOf {
+    uint32_t verdict;
+    bool grows;
+    uint32_t S2, K2;
+    uint32_t a, b, items;
+    bool edge_a, edge_b;
+};
+PMC_HD inline GrowOf grow_of(uint32_t isize, uint32_t lg, uint32_t off, uint32_t len) {
+    GrowOf g{};
+    const uint64_t end = (uint64_t)off + len, C = 1ull << lg;
+    g.S2 = isize;
+    g.K2 = (uint32_t)(((uint64_t)isize + C - 1) >> lg);
+    if (len == 0) {
+        g.verdict = kGrowSame;
+        return g;
+    }
+    if (end <= isize) {
+        const PatchOf p = patch_of(isize, lg, off, len);
+        g.a = p.a, g.b = p.b, g.items = p.items, g.edge_a = p.edge_a, g.edge_b = p.edge_b;
+        return g;
+    }
+    g.grows = true;
+    if (end > 0xFFFFFFFFull) {
+        g.verdict = kGrowArg;
+        return g;
+    }
+    const uint32_t K = g.K2;
+    g.S2 = (uint32_t)end;
+    g.K2 = (uint32_t)((end + C - 1) >> lg);
+    if (g.K2 > kIdxCrcMaxChunks) {
+        g.verdict = kGrowNoIndex;
+        return g;
+    }
+    g.a = K && (off >> lg) > K - 1 ? K - 1 : off >> lg;
+    g.b = g.K2 - 1;
+    g.items = g.K2 - g.a;
+    g.edge_a = (off < isize ? off : isize) > (uint64_t)g.a << lg;
+    return g;
+}
+
 // The member's CRC-32 folded from its K chunk CRCs as crc32_combine does, chunk lengths from isize and C = 2^lg:
 // crc = crc * x^(8 clen) + e[k] in GF(2)[x] mod P, reflected (the host form of the emit kernel's recurrence).
 inline uint32_t crc_multmodp_host(uint32_t a, uint32_t b) {

@@ -428,21 +428,27 @@ PMC_API int pmc_store_get_range_batch(pmc_store *s, const pmc_extent *ext, const
     return PMC_OK;
 }
 
-// Ranged set (include/pmc_codec.h pmc_store_set_range_batch): the rewrite call over the heap for the extents
-// that may carry an index; whole read, overlay and compress, in rounds of bounded scratch, for those it declined
-// and the small ones; then new extents by member length, the members compacted in, and the old extents released.
-PMC_API int pmc_store_set_range_batch(pmc_store *s, pmc_extent *ext, const uint8_t *src, const uint64_t *src_off,
-                                      const uint32_t *src_len, const uint32_t *range_off, uint32_t n, int32_t *rc) {
-    if (!s || (n && (!ext || !src || !src_off || !src_len || !range_off || !rc))) return PMC_E_ARG;
-    if (n == 0) return PMC_OK;
+// Ranged set (include/pmc_codec.h pmc_store_set_range_batch) and, with `grow`, growing set
+// (pmc_store_grow_range_batch): the rewrite or the grow call over the heap for the extents that may carry an index;
+// whole read into a value of the new length, overlay and compress, in rounds of bounded scratch, for those it
+// declined and the small ones; then new extents by member length, the members compacted in, and the old extents
+// released.  nraw: a value's length after the write (grown_len; without `grow` what it was).
+static int store_write_range(pmc_store *s, bool grow, const char *who, pmc_extent *ext, const uint8_t *src,
+                             const uint64_t *src_off, const uint32_t *src_len, const uint32_t *range_off, uint32_t n,
+                             int32_t *rc) {
     std::lock_guard<std::mutex> get_lock(s->get_mu);
     StoreCall call(s, s->put_mu);
     pmc_ctx *ctx = s->ctx;
     // live, in-bounds, distinct extents; an empty patch changes nothing
     std::unordered_map<uint64_t, uint32_t> seen;
+    std::vector<uint32_t> nraw(n, 0);
     for (uint32_t i = 0; i < n; i++) {
         const bool live = (ext[i].flags & 1) && ext[i].len;
-        rc[i] = live && (uint64_t)range_off[i] + src_len[i] <= ext[i].raw_len ? PMC_OK : PMC_E_ARG;
+        const uint64_t end = (uint64_t)range_off[i] + src_len[i];
+        const uint64_t after = src_len[i] ? grown_len(ext[i].raw_len, range_off[i], src_len[i]) : ext[i].raw_len;
+        const bool fits = grow ? src_len[i] == 0 || after <= kStoreGrowMax : end <= ext[i].raw_len;
+        rc[i] = live && fits ? PMC_OK : PMC_E_ARG;
+        nraw[i] = (uint32_t)after; // (<= 2^32 - 1 where fits)
         if (live) seen[ext[i].off]++;
     }
     std::vector<uint32_t> pick, full; // pick: chunk-path requests first, then the small ones
@@ -464,7 +470,7 @@ PMC_API int pmc_store_set_range_batch(pmc_store *s, pmc_extent *ext, const uint8
     uint64_t pbytes = 0, slots = 0;
     for (uint32_t k = 0; k < m; k++) {
         pbytes += src_len[pick[k]];
-        slots += round16(gzip_bound(ext[pick[k]].raw_len));
+        slots += round16(gzip_bound(nraw[pick[k]]));
     }
     const uint64_t pb = al256(pbytes + 16);
     int r = s->phost.ensure(meta + pb);
@@ -484,18 +490,19 @@ PMC_API int pmc_store_set_range_batch(pmc_store *s, pmc_extent *ext, const uint8
         memcpy(h_patch + po, src + src_off[i], src_len[i]);
         po += src_len[i];
         L.doff.h[k] = doff;
-        L.dcap.h[k] = (uint32_t)gzip_bound(ext[i].raw_len);
-        doff += round16(gzip_bound(ext[i].raw_len));
+        L.dcap.h[k] = (uint32_t)gzip_bound(nraw[i]);
+        doff += round16(gzip_bound(nraw[i]));
         L.dlen.h[k] = 0;
         L.rc.h[k] = k < mc ? PMC_OK : PMC_E_NO_INDEX; // (the small ones take the full path)
     }
     hipStream_t st = ctx->stream;
-    const HipOk ok{"pmc_store_set_range_batch"};
+    const HipOk ok{who};
     if (!ok(hipMemcpyAsync(dp, hp, meta + pbytes, hipMemcpyHostToDevice, st))) return fail_all(PMC_E_NO_DEVICE);
     // 1. the chunk path
     if (mc) {
-        r = pmc_gzip_rewrite_range_batch(ctx, (const uint8_t *)s->heap.p, L.soff.d, L.slen.d, d_patch, L.poff.d, L.plen.d,
-                                         L.roff.d, mc, d_slots, L.doff.d, L.dcap.d, L.dlen.d, L.rc.d, st);
+        r = (grow ? pmc_gzip_grow_range_batch : pmc_gzip_rewrite_range_batch)(
+            ctx, (const uint8_t *)s->heap.p, L.soff.d, L.slen.d, d_patch, L.poff.d, L.plen.d, L.roff.d, mc, d_slots,
+            L.doff.d, L.dcap.d, L.dlen.d, L.rc.d, st);
         if (r) return fail_all(r);
         if (!ok(hipMemcpyAsync(L.dlen.h, L.dlen.d, mc * 4ull, hipMemcpyDeviceToHost, st)) ||
             !ok(hipMemcpyAsync(L.rc.h, L.rc.d, mc * 4ull, hipMemcpyDeviceToHost, st)) || !ok(hipStreamSynchronize(st)))
@@ -505,19 +512,19 @@ PMC_API int pmc_store_set_range_batch(pmc_store *s, pmc_extent *ext, const uint8
     for (uint32_t k = 0; k < m; k++)
         if (L.rc.h[k] == PMC_E_NO_INDEX) {
             full.push_back(k);
-            raw.push_back(ext[pick[k]].raw_len);
+            raw.push_back(nraw[pick[k]]);
         }
     // 2. the full path, in rounds over `full`
     for (size_t w0 = 0; w0 < full.size();) {
         const FallbackRound R = cut_round(raw.data(), raw.size(), w0, kRangeFallbackBudget);
         const uint32_t q = (uint32_t)(R.end - w0);
-        // round staging: RangeSetRound's arrays | values
-        const uint64_t rmeta = RangeSetRound(q).meta;
+        // round staging: RangeWriteRound's arrays | values of the new lengths
+        const uint64_t rmeta = RangeWriteRound(q).meta;
         r = s->rhost.ensure(rmeta);
         if (!r) r = s->rdev.ensure(rmeta + R.bytes + 64);
         if (r) return fail_all(r);
         uint8_t *rh = (uint8_t *)s->rhost.p, *rd = (uint8_t *)s->rdev.p;
-        const RangeSetRound G(q, rh, rd);
+        const RangeWriteRound G(q, rh, rd);
         uint64_t at = 0;
         for (uint32_t j = 0; j < q; j++) {
             const uint32_t k = full[w0 + j], i = pick[k];
@@ -525,22 +532,25 @@ PMC_API int pmc_store_set_range_batch(pmc_store *s, pmc_extent *ext, const uint8
             G.slen.h[j] = ext[i].len;
             G.voff.h[j] = at;
             G.vcap.h[j] = ext[i].raw_len;
+            G.nlen.h[j] = nraw[i];
             G.cut.h[j] = at + range_off[i];
             G.poff.h[j] = L.poff.h[k];
             G.plen.h[j] = src_len[i];
             G.doff.h[j] = L.doff.h[k];
             G.dcap.h[j] = L.dcap.h[k];
-            at += round16(ext[i].raw_len);
+            at += round16(nraw[i]);
         }
         uint8_t *d_vals = rd + rmeta;
         if (!ok(hipMemcpyAsync(rd, rh, rmeta, hipMemcpyHostToDevice, st))) return fail_all(PMC_E_NO_DEVICE);
+        // (a growing set: the bytes between a value's old end and its patch are zero)
+        if (grow && !ok(hipMemsetAsync(d_vals, 0, R.bytes, st))) return fail_all(PMC_E_NO_DEVICE);
         r = pmc_gzip_decompress_batch(ctx, (const uint8_t *)s->heap.p, G.soff.d, G.slen.d, q, d_vals, G.voff.d, G.vcap.d,
                                       G.vlen.d, G.vrc.d, (uint32_t)R.max_raw, st);
         if (r) return fail_all(r);
         // the patches over the values that decoded (rc 0), then the values compressed into their slots
         launch_compact(st, q, d_patch, G.poff.d, G.plen.d, G.vrc.d, G.cut.d, d_vals);
         if (!ok(hipGetLastError())) return fail_all(PMC_E_NO_DEVICE);
-        r = pmc_gzip_compress_batch(ctx, d_vals, G.voff.d, G.vcap.d, q, d_slots, G.doff.d, G.dcap.d, G.dlen.d, G.rc.d,
+        r = pmc_gzip_compress_batch(ctx, d_vals, G.voff.d, G.nlen.d, q, d_slots, G.doff.d, G.dcap.d, G.dlen.d, G.rc.d,
                                     (uint32_t)R.max_raw, st);
         if (r) return fail_all(r);
         if (!ok(hipMemcpyAsync(G.vlen_vrc.h, G.vlen_vrc.d, G.vlen_vrc.bytes, hipMemcpyDeviceToHost, st)) ||
@@ -560,7 +570,7 @@ PMC_API int pmc_store_set_range_batch(pmc_store *s, pmc_extent *ext, const uint8
     std::vector<pmc_extent> fresh(m, pmc_extent{0, 0, 0, 0, 0});
     const bool moved = store_commit(
         s, ok, st, m, d_slots, L.doff, L.dlen, L.rc, L.noff, true, [&](uint32_t k) -> pmc_extent & { return fresh[k]; },
-        [&](uint32_t k) { return ext[pick[k]].raw_len; });
+        [&](uint32_t k) { return nraw[pick[k]]; });
     std::lock_guard<std::mutex> a(s->alloc_mu);
     for (uint32_t k = 0; k < m; k++) {
         const uint32_t i = pick[k];
@@ -572,6 +582,29 @@ PMC_API int pmc_store_set_range_batch(pmc_store *s, pmc_extent *ext, const uint8
         ext[i] = fresh[k];
     }
     return moved ? PMC_OK : PMC_E_NO_DEVICE;
+}
+
+PMC_API int pmc_store_set_range_batch(pmc_store *s, pmc_extent *ext, const uint8_t *src, const uint64_t *src_off,
+                                      const uint32_t *src_len, const uint32_t *range_off, uint32_t n, int32_t *rc) {
+    if (!s || (n && (!ext || !src || !src_off || !src_len || !range_off || !rc))) return PMC_E_ARG;
+    if (n == 0) return PMC_OK;
+    return store_write_range(s, false, "pmc_store_set_range_batch", ext, src, src_off, src_len, range_off, n, rc);
+}
+
+PMC_API int pmc_store_grow_range_batch(pmc_store *s, pmc_extent *ext, const uint8_t *src, const uint64_t *src_off,
+                                       const uint32_t *src_len, const uint32_t *range_off, uint32_t n, int32_t *rc) {
+    if (!s || (n && (!ext || !src || !src_off || !src_len || !range_off || !rc))) return PMC_E_ARG;
+    if (n == 0) return PMC_OK;
+    return store_write_range(s, true, "pmc_store_grow_range_batch", ext, src, src_off, src_len, range_off, n, rc);
+}
+
+PMC_API int pmc_store_append_batch(pmc_store *s, pmc_extent *ext, const uint8_t *src, const uint64_t *src_off,
+                                   const uint32_t *src_len, uint32_t n, int32_t *rc) {
+    if (!s || (n && (!ext || !src || !src_off || !src_len || !rc))) return PMC_E_ARG;
+    if (n == 0) return PMC_OK;
+    std::vector<uint32_t> at(n);
+    for (uint32_t i = 0; i < n; i++) at[i] = ext[i].raw_len;
+    return store_write_range(s, true, "pmc_store_append_batch", ext, src, src_off, src_len, at.data(), n, rc);
 }
 
 PMC_API int pmc_store_read_members(pmc_store *s, const pmc_extent *ext, uint32_t n, uint8_t *dst,

@@ -151,6 +151,13 @@ struct RangeSetRound { // its fallback round (v*: the whole values it decodes): 
     StageSpan vlen_vrc = c.span(vlen, vrc), dlen_rc = c.span(dlen, rc);
     uint64_t meta = c.meta;
 };
+// the round as the ranged and growing sets use it: behind RangeSetRound's arrays the values' new lengths (vcap:
+// what the old member decodes to; nlen: what is compressed -- the same where the value does not grow)
+struct RangeWriteRound : RangeSetRound {
+    explicit RangeWriteRound(uint64_t m, void *host = nullptr, void *dev = nullptr) : RangeSetRound(m, host, dev) {}
+    StageArr<uint32_t> nlen = c.u32();
+    uint64_t meta = c.meta;
+};
 struct MembersStage { // pmc_store_read_members: ... | members
     PMC_STAGE(MembersStage);
     StageArr<uint64_t> soff = c.u64(), poff = c.u64();
@@ -188,6 +195,14 @@ inline void frame_write(uint8_t *p, int frame, uint32_t L) {
     } else if (frame == PMC_FRAME_CUSTOM) {
         p[L] = 0x1F;
     }
+}
+
+// ---- growing sets ------------------------------------------------------------------------------------------
+// A value of raw_len bytes after a write of len bytes at off (len > 0): max(raw_len, off + len) bytes.  The store
+// takes no value longer than the server's MAX_REQUEST_SIZE, Redis's own limit for APPEND and SETRANGE.
+constexpr uint64_t kStoreGrowMax = 536870912;
+inline uint64_t grown_len(uint32_t raw_len, uint32_t off, uint32_t len) {
+    return std::max<uint64_t>(raw_len, (uint64_t)off + len);
 }
 
 // ---- fallback rounds ---------------------------------------------------------------------------------------

@@ -116,8 +116,11 @@ SIGNATURES = {
     "pmc_ctx_get_range_verify": (_c.c_int, [_p, _c.POINTER(_c.c_int)]),
     "pmc_ctx_range_verify_counts": (_c.c_int, [_p, _c.POINTER(_u64)]),
     "pmc_gzip_rewrite_range_batch": (_c.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _u32, _p, _p, _p, _p, _p, _p]),
+    "pmc_gzip_grow_range_batch": (_c.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _u32, _p, _p, _p, _p, _p, _p]),
     "pmc_ctx_rewrite_counts": (_c.c_int, [_p, _c.POINTER(_u64)]),
     "pmc_store_set_range_batch": (_c.c_int, [_p, _p, _p, _p, _p, _p, _u32, _p]),
+    "pmc_store_grow_range_batch": (_c.c_int, [_p, _p, _p, _p, _p, _p, _u32, _p]),
+    "pmc_store_append_batch": (_c.c_int, [_p, _p, _p, _p, _p, _u32, _p]),
 }
 
 # compression levels (include/pmc_codec.h PMC_LEVEL_*)
@@ -484,6 +487,17 @@ class Context:
         if r != 0:
             raise CodecUnavailable(f"pmc_gzip_rewrite_range_batch = {r}: {last_error()}")
 
+    def grow_range_device(self, src, src_off, src_len, patch, patch_off, patch_len, range_off, dst, dst_off, dst_cap,
+                          dst_len, rc, stream=0):
+        """rewrite_range_device for a patch that may reach past the value's end: the value grows to range_off +
+        patch_len bytes, zeros between its old end and the patch; the chunks before the first touched one are copied
+        (include/pmc_codec.h "growing writes")."""
+        r = lib().pmc_gzip_grow_range_batch(self.handle, _ptr(src), _ptr(src_off), _ptr(src_len), _ptr(patch),
+                                            _ptr(patch_off), _ptr(patch_len), _ptr(range_off), _n(src_len), _ptr(dst),
+                                            _ptr(dst_off), _ptr(dst_cap), _ptr(dst_len), _ptr(rc), stream)
+        if r != 0:
+            raise CodecUnavailable(f"pmc_gzip_grow_range_batch = {r}: {last_error()}")
+
     def rewrite_counts(self):
         """{served, declined, decoded, compressed, copied}: rewrite requests answered OK / answered E_NO_INDEX, and
         the chunks decoded, compressed again and copied verbatim (include/pmc_codec.h pmc_ctx_rewrite_counts)."""
@@ -614,6 +628,32 @@ class Store:
         -> rc list; ext[i] becomes the new extent where rc is 0 and stays as it is otherwise.  Compresses only the
         chunks a patch touches where the member is indexed with chunk CRCs, the whole value otherwise
         (pmc_store_set_range_batch)."""
+        return self._write_range("pmc_store_set_range_batch", ext, patches, n)
+
+    def grow_range(self, ext, patches, n=None):
+        """set_range for patches that may reach past the value's end (Redis SETRANGE): the value grows, zeros between
+        its old end and the patch (pmc_store_grow_range_batch)."""
+        return self._write_range("pmc_store_grow_range_batch", ext, patches, n)
+
+    def append(self, ext, values, n=None):
+        """values: n byte strings, each put behind extent i's value (Redis APPEND) -> rc list
+        (pmc_store_append_batch)."""
+        import numpy as np
+        n = len(ext) if n is None else n
+        if n == 0:
+            return []
+        assert len(values) == n, (len(values), n)
+        lens = np.array([len(v) for v in values], dtype=np.uint32)
+        off = np.zeros(n, dtype=np.uint64)
+        off[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+        rc = np.zeros(n, dtype=np.int32)
+        r = lib().pmc_store_append_batch(self.handle, ext, b"".join(bytes(v) for v in values) + b"\0", off.ctypes.data,
+                                         lens.ctypes.data, n, rc.ctypes.data)
+        if r != 0:
+            raise CodecUnavailable(f"pmc_store_append_batch = {r}: {last_error()}")
+        return [int(x) for x in rc]
+
+    def _write_range(self, name, ext, patches, n):
         import numpy as np
         n = len(ext) if n is None else n
         if n == 0:
@@ -624,10 +664,10 @@ class Store:
         off[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
         roff = np.array([p[0] for p in patches], dtype=np.uint32)
         rc = np.zeros(n, dtype=np.int32)
-        r = lib().pmc_store_set_range_batch(self.handle, ext, b"".join(bytes(p[1]) for p in patches) + b"\0",
-                                            off.ctypes.data, lens.ctypes.data, roff.ctypes.data, n, rc.ctypes.data)
+        r = getattr(lib(), name)(self.handle, ext, b"".join(bytes(p[1]) for p in patches) + b"\0", off.ctypes.data,
+                                 lens.ctypes.data, roff.ctypes.data, n, rc.ctypes.data)
         if r != 0:
-            raise CodecUnavailable(f"pmc_store_set_range_batch = {r}: {last_error()}")
+            raise CodecUnavailable(f"{name} = {r}: {last_error()}")
         return [int(x) for x in rc]
 
     def members(self, ext, n=None):

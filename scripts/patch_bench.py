@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Ranged writes against the same update done without them (include/pmc_codec.h "ranged writes").
+"""Ranged and growing writes against the same update done without them (include/pmc_codec.h "ranged writes",
+"growing writes").
 
 Device-resident: n JSON-slice values of vlen bytes (bench.py's generator and seed) are compressed once at
 PMC_LEVEL_FAST_ALL with the index and index_crc switches on.  Then, for every patch shape, two ways of applying one
@@ -12,9 +13,13 @@ JSON line: per shape the ms per call of every run, the chunks decoded / compress
 the medians, whether the slowest rewrite run beat the fastest full-sequence run, and the per-kind kernel times of
 one profiled call (the rewrite's scan and tables run under `order`, its edge decode under `inflate_lane`, overlay
 and parse under `deflate_large`, emit, finish and copy under `deflate_large_emit`).
+The shapes append64 and append_chunk put 64 bytes, or one chunk, behind every value: there "rewrite" is
+pmc_gzip_grow_range_batch, and the full sequence decompresses the whole member into a slot of the new length, copies
+the tail in on the device and compresses the whole new value.
 
     python scripts/patch_bench.py --n 1000 --vlen 1048576 --shapes in64,across4k,chunk,whole
     python scripts/patch_bench.py --n 40000 --vlen 65536 --shapes in64
+    python scripts/patch_bench.py --n 1000 --vlen 1048576 --shapes append64,append_chunk
 """
 import argparse
 import ctypes
@@ -72,6 +77,10 @@ def shape_of(name, vlen, n, rng):
         return C, rng.integers(0, k, n) * C
     if name == "whole":
         return vlen, np.zeros(n, dtype=np.int64)
+    if name == "append64":    # 64 bytes behind the value
+        return 64, np.full(n, vlen, dtype=np.int64)
+    if name == "append_chunk":  # one chunk behind it
+        return C, np.full(n, vlen, dtype=np.int64)
     raise SystemExit(f"unknown shape {name}")
 
 
@@ -133,22 +142,46 @@ def main():
         poff = torch.arange(n, dtype=torch.int64, device=dev) * ln
         plen = torch.full((n,), ln, dtype=torch.int32, device=dev)
         roff = torch.from_numpy(o.astype(np.uint32).view(np.int32).copy()).to(dev)
-        if ln == vlen:
+        grows = name.startswith("append")
+        if grows:  # values of glen bytes: their own value slots and member slots
+            glen = vlen + ln
+            goff = torch.arange(n, dtype=torch.int64, device=dev) * glen
+            glens = torch.full((n,), glen, dtype=torch.int32, device=dev)
+            gcap = pmc_codec.gzip_bound(glen)
+            gstride = (gcap + 15) // 16 * 16
+            gcoff = torch.arange(n, dtype=torch.int64, device=dev) * gstride
+            gccap = torch.full((n,), gcap, dtype=torch.int32, device=dev)
+            gback = torch.empty(n * glen + 16, dtype=torch.uint8, device=dev)
+            new_g = torch.empty(n * gstride + 16, dtype=torch.uint8, device=dev)
+            new_h = torch.empty(n * gstride + 16, dtype=torch.uint8, device=dev)
+            idx = ((goff + vlen)[:, None] + torch.arange(ln, device=dev)[None, :]).reshape(-1)
+        elif ln == vlen:
             idx = None
         else:
             idx = (off + torch.from_numpy(o.astype(np.int64)).to(dev))[:, None] + torch.arange(ln, device=dev)[None, :]
             idx = idx.reshape(-1)
 
-        def rewrite():
+        def rewrite_in():
             ctx.rewrite_range_device(comp, coff, clen, patches, poff, plen, roff, new_r, coff, ccap, rlen_r, rc_r, sh)
 
-        def full():
+        def full_in():
             ctx.decompress_device(comp, coff, clen, back, off, lens, blen, brc, vlen, sh)
             if idx is None:
                 back[:n * vlen].copy_(patches[:n * ln])
             else:
                 back[idx] = patches[:n * ln]
             ctx.compress_device(back, off, lens, new_f, coff, ccap, rlen_f, rc_f, vlen, sh)
+
+        def rewrite_grow():
+            ctx.grow_range_device(comp, coff, clen, patches, poff, plen, roff, new_g, gcoff, gccap, rlen_r, rc_r, sh)
+
+        def full_grow():
+            ctx.decompress_device(comp, coff, clen, gback, goff, glens, blen, brc, glen, sh)
+            gback[idx] = patches[:n * ln]
+            ctx.compress_device(gback, goff, glens, new_h, gcoff, gccap, rlen_f, rc_f, glen, sh)
+
+        rewrite, full = (rewrite_grow, full_grow) if grows else (rewrite_in, full_in)
+        out_r, out_f, out_off = (new_g, new_h, gcoff) if grows else (new_r, new_f, coff)
 
         c0 = ctx.rewrite_counts()
         rewrite()
@@ -158,7 +191,7 @@ def main():
         torch.cuda.synchronize()
         assert int((rc_r != 0).sum()) == 0 and int((rc_f != 0).sum()) == 0 and int((brc != 0).sum()) == 0
         mism.zero_()
-        assert L.pmc_compare_values(new_r.data_ptr(), coff.data_ptr(), new_f.data_ptr(), coff.data_ptr(),
+        assert L.pmc_compare_values(out_r.data_ptr(), out_off.data_ptr(), out_f.data_ptr(), out_off.data_ptr(),
                                     rlen_r.data_ptr(), rlen_f.data_ptr(), n, mism.data_ptr(), sh) == 0
         torch.cuda.synchronize()
         assert int(mism[0]) == 0, "the rewrite's members differ from the full sequence's"
@@ -178,6 +211,8 @@ def main():
         leg["full_kernels"] = kernel_times(ctx, full)
         res["shapes"][name] = leg
         del patches, idx
+        if grows:
+            del gback, new_g, new_h
     ctx.close()
     print(json.dumps(res))
 
