@@ -13,14 +13,8 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
-#include <chrono>
-#include <condition_variable>
-#include <functional>
 #include <mutex>
 #include <string>
-#include <thread>
-
-#include <unistd.h>
 
 #include "../../include/pmc_codec.h"
 #include "pmc_device.hpp"
@@ -1171,13 +1165,70 @@ static int compress_batch_body(pmc_ctx *ctx, const uint8_t *src, const uint64_t 
     return PMC_OK;
 }
 
-// ---- a decompress call: plan_inflate (pmc_plan.hpp: which stages run, their grids and scratch, and why) ->
-// order, record kernel, lane passes, chunk pass, CRC check, wave kernels --------------------------------------
+// ---- prefix sums (the chunk pass, the ranged calls, pmc_host.hip's compacted chunks) --------------------------
 namespace {
-int scan_u32(const uint32_t *v, const int32_t *rc, uint32_t n, uint64_t *out, uint64_t *bsum, hipStream_t st);
-constexpr uint32_t kIdxScanBlock = 1024; // (= kScanBlock: scan_u32's block sums, one per so many members)
+// Exclusive prefix sum of v[i] (0 where rc[i] != 0, if rc is given) into out[]; kScanBlock values per
+// block, block totals to bsum[] (scan_blocks_kernel turns them into block bases, bsum[nb] = total).
+constexpr uint32_t kScanBlock = 1024;
+static_assert(kScanBlock == kIdxScanBlock, "the plans size scan_u32's block sums");
+__global__ __launch_bounds__(kScanBlock) void scan_local_kernel(const uint32_t *v, const int32_t *rc, uint32_t n,
+                                                                 uint64_t *out, uint64_t *bsum) {
+    __shared__ uint64_t s[kScanBlock];
+    const uint32_t t = threadIdx.x, i = blockIdx.x * kScanBlock + t;
+    const uint64_t x = i < n && !(rc && rc[i] != 0) ? v[i] : 0;
+    s[t] = x;
+    __syncthreads();
+    for (uint32_t d = 1; d < kScanBlock; d <<= 1) {
+        uint64_t y = t >= d ? s[t - d] : 0;
+        __syncthreads();
+        s[t] += y;
+        __syncthreads();
+    }
+    if (i < n) out[i] = s[t] - x;
+    if (t == kScanBlock - 1) bsum[blockIdx.x] = s[t];
+}
+
+__global__ __launch_bounds__(kScanBlock) void scan_blocks_kernel(uint64_t *bsum, uint32_t nb) {
+    __shared__ uint64_t s[kScanBlock];
+    __shared__ uint64_t carry;
+    const uint32_t t = threadIdx.x;
+    if (t == 0) carry = 0;
+    __syncthreads();
+    for (uint32_t base = 0; base < nb; base += kScanBlock) {
+        const uint64_t x = base + t < nb ? bsum[base + t] : 0;
+        s[t] = x;
+        __syncthreads();
+        for (uint32_t d = 1; d < kScanBlock; d <<= 1) {
+            uint64_t y = t >= d ? s[t - d] : 0;
+            __syncthreads();
+            s[t] += y;
+            __syncthreads();
+        }
+        if (base + t < nb) bsum[base + t] = carry + s[t] - x;
+        __syncthreads();
+        if (t == kScanBlock - 1) carry += s[t];
+        __syncthreads();
+    }
+    if (t == 0) bsum[nb] = carry;
+}
+
+__global__ __launch_bounds__(kScanBlock) void scan_add_kernel(uint64_t *out, uint32_t n, const uint64_t *bsum) {
+    const uint32_t i = blockIdx.x * kScanBlock + threadIdx.x;
+    if (i < n) out[i] += bsum[blockIdx.x];
+}
+
+int scan_u32(const uint32_t *v, const int32_t *rc, uint32_t n, uint64_t *out, uint64_t *bsum, hipStream_t st) {
+    const uint32_t nb = (n + kScanBlock - 1) / kScanBlock;
+    hipLaunchKernelGGL(scan_local_kernel, dim3(nb), dim3(kScanBlock), 0, st, v, rc, n, out, bsum);
+    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(kScanBlock), 0, st, bsum, nb);
+    hipLaunchKernelGGL(scan_add_kernel, dim3(nb), dim3(kScanBlock), 0, st, out, n, bsum);
+    HIP_TRY(hipGetLastError());
+    return PMC_OK;
+}
 } // namespace
 
+// ---- a decompress call: plan_inflate (pmc_plan.hpp: which stages run, their grids and scratch, and why) ->
+// order, record kernel, lane passes, chunk pass, CRC check, wave kernels --------------------------------------
 // the A/B switches of the decompress path, read once per process
 struct InflateEnv {
     bool wave_only, no_order, no_rec; // PMC_INFLATE_WAVE=1, PMC_INFLATE_ORDER=0, PMC_INFLATE_REC=0
@@ -1803,616 +1854,6 @@ PMC_API int pmc_gzip_isize_batch(pmc_ctx *ctx, const uint8_t *src, const uint64_
     hipLaunchKernelGGL(isize_kernel, dim3(std::min<uint32_t>((n + 255) / 256, 4096)), dim3(256), 0,
                        (hipStream_t)stream, src, src_off, src_len, n, isize);
     return hipGetLastError() == hipSuccess ? PMC_OK : PMC_E_NO_DEVICE;
-}
-
-// ---- host-resident batches: pinned staging, H2D -> kernels -> D2H -------------------
-namespace {
-enum Dir { kCompress, kDecompress };
-
-// A host-API call holds its context's lock (the staging buffers, pinned pipe and default context
-// are shared by every thread that calls the drop-in) and leaves the caller's current device as
-// it found it.
-struct HostCall {
-    std::lock_guard<std::mutex> lock;
-    int prev = -1;
-    explicit HostCall(pmc_ctx *ctx) : lock(ctx->host_mu) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    }
-    ~HostCall() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-// Per-value copies between the caller's buffers and the staging area: one job per value, spread over a
-// small pool of persistent host threads once a call moves enough bytes that one core's memcpy (~10 GB/s)
-// would show beside the kernels (a 4,096 x 4 KiB batch is 16 MiB in and 17 MiB of slots out): one part per
-// MiB, at most 8 parts (PMC_HOST_THREADS overrides).  Threads spawned per call cost more than they saved
-// at 16 parts (unpack 0.43 -> 0.7 ms), so the pool's workers live for the process and wait on a condition.
-class CopyPool {
-  public:
-    static CopyPool &get() {
-        static CopyPool *p = new CopyPool(); // (never destroyed: workers may outlive static destructors)
-        return *p;
-    }
-    unsigned parts() const { return nthreads + 1; }
-    // runs part(k) for k = 0 .. t - 1 (t <= parts()), part 0 on the calling thread
-    template <class F>
-    void run(unsigned t, F part) {
-        // Inline on the calling thread when: one part; a process forked after the pool started (the child
-        // has no workers); or the pool is busy with another context's copies (a server's SET and
-        // GET contexts copy at the same time: the second caller does its own copies instead of waiting).
-        std::unique_lock<std::mutex> one(run_mu, std::defer_lock);
-        if (t <= 1 || getpid() != owner || !one.try_lock()) {
-            for (unsigned k = 0; k < t; k++) part(k);
-            return;
-        }
-        std::unique_lock<std::mutex> lk(mu);
-        fn = [&part](unsigned k) { part(k); };
-        want = t - 1;
-        taken = 0;
-        left = t - 1;
-        gen++;
-        cv.notify_all();
-        lk.unlock();
-        part(0u);
-        lk.lock();
-        done.wait(lk, [&] { return left == 0; });
-        fn = nullptr;
-    }
-
-  private:
-    CopyPool() : owner(getpid()) {
-        const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-        const unsigned cap = getenv("PMC_HOST_THREADS") ? (unsigned)std::max(1, atoi(getenv("PMC_HOST_THREADS")))
-                                                        : std::min(8u, hw);
-        nthreads = cap - 1;
-        for (unsigned k = 0; k < nthreads; k++) std::thread([this] { loop(); }).detach();
-    }
-    void loop() {
-        uint64_t seen = 0;
-        std::unique_lock<std::mutex> lk(mu);
-        for (;;) {
-            cv.wait(lk, [&] { return gen != seen && taken < want; });
-            seen = gen;
-            const unsigned k = ++taken; // parts 1 .. want
-            auto f = fn;
-            lk.unlock();
-            f(k);
-            lk.lock();
-            if (--left == 0) done.notify_one();
-        }
-    }
-    const pid_t owner; // the process whose threads these workers are
-    std::mutex mu, run_mu;
-    std::condition_variable cv, done;
-    std::function<void(unsigned)> fn;
-    unsigned nthreads = 0, want = 0, taken = 0, left = 0;
-    uint64_t gen = 0;
-};
-
-template <class F>
-void par_values(uint32_t n, uint64_t bytes, F job) {
-    CopyPool &P = CopyPool::get();
-    const unsigned t = (unsigned)std::min<uint64_t>({(uint64_t)P.parts(), (uint64_t)n, std::max<uint64_t>(1, bytes >> 20)});
-    P.run(t, [&](unsigned k) {
-        const uint32_t a = (uint32_t)((uint64_t)n * k / t), b = (uint32_t)((uint64_t)n * (k + 1) / t);
-        for (uint32_t i = a; i < b; i++) job(i);
-    });
-}
-
-double now_us() {
-    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-// (the caller holds ctx->host_mu; force_pipeline: the throughput route whatever the batch's size)
-int host_batch_locked(pmc_ctx *ctx, Dir dir, const uint8_t *src, const uint64_t *src_off, const uint32_t *src_len,
-                      uint32_t n, uint8_t *dst, const uint64_t *dst_off, const uint32_t *dst_cap, uint32_t *dst_len,
-                      int32_t *rc, bool force_pipeline) {
-    if (n == 0) return PMC_OK;
-    static const bool trace = getenv("PMC_HOST_TRACE") && atoi(getenv("PMC_HOST_TRACE"));
-    double t[8] = {};
-    if (trace) t[0] = now_us();
-    HIP_TRY(hipSetDevice(ctx->device));
-    // packed device layout, in the order of the two copies: [offsets, lengths, caps | source bytes]
-    // go down in one H2D, [output lengths, verdicts | output bytes] come back in one D2H
-    uint64_t in_bytes = 0, out_bytes = 0, max_len = 0, max_in = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        in_bytes += src_len[i];
-        out_bytes += dst_cap[i];
-        uint64_t m = dir == kCompress ? src_len[i] : dst_cap[i];
-        max_len = std::max(max_len, m);
-        max_in = std::max<uint64_t>(max_in, src_len[i]);
-    }
-    auto al = [](uint64_t x) { return (x + 255) & ~(uint64_t)255; };
-    const uint64_t down = al(n * 8ull) * 2 + al(n * 4ull) * 2 + al(in_bytes + 16);
-    const uint64_t up = al(n * 4ull) * 2 + al(out_bytes + 16);
-    // Routing (limits measured with scripts/few_sweep.py).  Compress: up to 1,024 values of <= 4 KiB the
-    // one-kernel path (deflate_small_kernel) beats the pipeline; above 4 KiB the wave-per-value kernel would
-    // work from HBM, far slower than the split pipeline's large pass.  Decompress: the wave-per-member
-    // inflate kernel holds a member's output in LDS up to kInflateLdsOut (48 KiB), so a member up
-    // to that size stays on the latency path (a 30 KB member: 0.81 ms there against 3.8 ms through the
-    // pipeline); its batch limit is 4,096 members / 16 MiB of output (inflate_latency:
-    // round 5 measured the wave kernel still 2x ahead there).
-    const uint64_t lat_max = latency_max_len(), lat_batch = latency_batch();
-    // (a fast-level compress always takes the pipeline: the one-kernel path is exact only)
-    const bool fast = dir == kCompress && level_is_fast(ctx->level) && ctx->lane_order_ok;
-    const bool latency = !force_pipeline && (dir == kCompress ? !fast && n <= lat_batch && max_len <= lat_max
-                                                              : inflate_latency(n, max_len, out_bytes, ctx->cus, lat_batch,
-                                                                                lat_max, false, kInflateLdsOut));
-    ctx->path_calls[(latency ? 0 : 2) + (dir == kCompress ? 0 : 1)]++;
-    // The latency path's kernel reads its inputs from, and writes its outputs to, coherent host memory in
-    // place: no H2D / D2H copies (each a runtime copy kernel of its own) around its one launch.
-    const bool zc = latency;
-    uint8_t *hp, *dp;
-    int r;
-    if (zc) {
-        ctx->zc.flags = hipHostMallocCoherent;
-        const void *old = ctx->zc.p;
-        r = ctx->zc.ensure(down + up);
-        if (r) return r;
-        if (ctx->zc.p != old) ctx->zc_dev = nullptr; // (a new buffer: its device address is looked up below)
-        if (!ctx->zc_dev) {
-            void *d = nullptr;
-            HIP_TRY(hipHostGetDevicePointer(&d, ctx->zc.p, 0));
-            ctx->zc_dev = d;
-        }
-        hp = (uint8_t *)ctx->zc.p;
-        dp = (uint8_t *)ctx->zc_dev;
-    } else {
-        r = ctx->pinned.ensure(down + up);
-        if (r) return r;
-        r = ctx->staging.ensure(down + up);
-        if (r) return r;
-        hp = (uint8_t *)ctx->pinned.p;
-        dp = (uint8_t *)ctx->staging.p;
-    }
-    uint64_t o = 0;
-    uint64_t *h_soff = (uint64_t *)(hp + o), *d_soff = (uint64_t *)(dp + o);
-    o += al(n * 8ull);
-    uint64_t *h_doff = (uint64_t *)(hp + o), *d_doff = (uint64_t *)(dp + o);
-    o += al(n * 8ull);
-    uint32_t *h_slen = (uint32_t *)(hp + o), *d_slen = (uint32_t *)(dp + o);
-    o += al(n * 4ull);
-    uint32_t *h_dcap = (uint32_t *)(hp + o), *d_dcap = (uint32_t *)(dp + o);
-    o += al(n * 4ull);
-    uint8_t *h_src = hp + o, *d_src = dp + o;
-    o += al(in_bytes + 16);
-    uint32_t *h_dlen = (uint32_t *)(hp + o), *d_dlen = (uint32_t *)(dp + o);
-    o += al(n * 4ull);
-    int32_t *h_rc = (int32_t *)(hp + o), *d_rc = (int32_t *)(dp + o);
-    o += al(n * 4ull);
-    uint8_t *h_dst = hp + o, *d_dst = dp + o;
-    uint64_t so = 0, doff = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        h_soff[i] = so;
-        h_slen[i] = src_len[i];
-        so += src_len[i];
-        h_doff[i] = doff;
-        h_dcap[i] = dst_cap[i];
-        doff += dst_cap[i];
-    }
-    par_values(n, in_bytes, [&](uint32_t i) { memcpy(h_src + h_soff[i], src + src_off[i], src_len[i]); });
-    if (trace) t[1] = now_us();
-    hipStream_t st = ctx->stream;
-    if (!zc) HIP_TRY(hipMemcpyAsync(dp, hp, down, hipMemcpyHostToDevice, st));
-    auto run = [&](bool lat) -> int {
-        const int d = dir == kCompress ? 0 : 1;
-        std::lock_guard<std::recursive_mutex> dir_lock(ctx->dir_mu[d]);
-        int e = dir_enter(ctx, d, st);
-        if (!e) {
-            if (dir == kCompress)
-                e = compress_batch_body(ctx, d_src, d_soff, d_slen, n, d_dst, d_doff, d_dcap, d_dlen, d_rc,
-                                        (uint32_t)max_len, st, lat);
-            else  // the wave kernels' HBM variant only for members the LDS image cannot hold
-                e = decompress_batch_body(ctx, d_src, d_soff, d_slen, n, d_dst, d_doff, d_dcap, d_dlen, d_rc,
-                                          (uint32_t)max_len, st, lat,
-                                          inflate_need_hbm(lat, max_len, max_in, kInflateLdsOut));
-            const int e2 = dir_leave(ctx, d, st);
-            if (!e) e = e2;
-        }
-        return e;
-    };
-    r = run(latency);
-    if (r) {
-        // kernels already queued may still read or write the staging (in zero-copy mode the host
-        // buffers themselves), which the next call refills: let them drain before returning
-        (void)hipStreamSynchronize(st);
-        return r;
-    }
-    if (trace) t[2] = now_us();
-    if (!zc) HIP_TRY(hipMemcpyAsync(h_dlen, d_dlen, up, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    // The latency path launches no retry pass: the values its kernel declined (a lane-order guard fired)
-    // are redone, alone, by a pipeline call (its gated HBM pass), straight into the caller's buffers.
-    std::vector<uint32_t> redo;
-    if (zc && dir == kCompress)
-        for (uint32_t i = 0; i < n; i++)
-            if (h_rc[i] == kDeflateRetry) redo.push_back(i);
-    std::vector<uint8_t> redone(redo.empty() ? 0 : n, 0);
-    if (!redo.empty()) {
-        ctx->latency_redone++;
-        const uint32_t m = (uint32_t)redo.size();
-        std::vector<uint64_t> r_soff(m), r_doff(m);
-        std::vector<uint32_t> r_slen(m), r_cap(m), r_dlen(m);
-        std::vector<int32_t> r_rc(m);
-        for (uint32_t k = 0; k < m; k++) {
-            const uint32_t i = redo[k];
-            r_soff[k] = src_off[i];
-            r_slen[k] = src_len[i];
-            r_cap[k] = dst_cap[i];
-            r_doff[k] = dst_off ? dst_off[i] : h_doff[i];
-            redone[i] = 1;
-        }
-        if ((r = host_batch_locked(ctx, dir, src, r_soff.data(), r_slen.data(), m, dst, r_doff.data(), r_cap.data(),
-                                   r_dlen.data(), r_rc.data(), true)))
-            return r;
-        for (uint32_t k = 0; k < m; k++) {
-            h_rc[redo[k]] = r_rc[k];
-            h_dlen[redo[k]] = r_dlen[k];
-        }
-    }
-    if (trace) t[3] = now_us();
-    uint64_t moved = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        rc[i] = h_rc[i];
-        dst_len[i] = h_dlen[i];
-        if (h_rc[i] == 0 && (redone.empty() || !redone[i])) moved += h_dlen[i];
-    }
-    par_values(n, moved, [&](uint32_t i) {
-        if (h_rc[i] != 0 || (!redone.empty() && redone[i])) return; // (redone values are in place already)
-        uint64_t to = dst_off ? dst_off[i] : h_doff[i];
-        memcpy(dst + to, h_dst + h_doff[i], h_dlen[i]);
-    });
-    if (trace) {
-        t[4] = now_us();
-        fprintf(stderr,
-                "pmc_host_trace %s n=%u in=%llu out=%llu path=%s stage_us=%.1f enqueue_us=%.1f wait_us=%.1f "
-                "unpack_us=%.1f total_us=%.1f\n",
-                dir == kCompress ? "compress" : "decompress", n, (unsigned long long)in_bytes,
-                (unsigned long long)moved, latency ? "latency" : "pipeline", t[1] - t[0], t[2] - t[1], t[3] - t[2],
-                t[4] - t[3], t[4] - t[0]);
-    }
-    return PMC_OK;
-}
-
-int host_batch(pmc_ctx *ctx, Dir dir, const uint8_t *src, const uint64_t *src_off, const uint32_t *src_len,
-               uint32_t n, uint8_t *dst, const uint64_t *dst_off, const uint32_t *dst_cap, uint32_t *dst_len,
-               int32_t *rc) {
-    if (!ctx) return PMC_E_ARG;
-    if (n == 0) return PMC_OK;
-    HostCall guard(ctx);
-    return host_batch_locked(ctx, dir, src, src_off, src_len, n, dst, dst_off, dst_cap, dst_len, rc, false);
-}
-
-// Rebases one chunk's offsets onto its device copy: src_off -= sb, dst_off -= db (dst_off may be null).
-__global__ void rebase_kernel(uint64_t *soff, uint64_t *doff, uint32_t n, uint64_t sb, uint64_t db) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        soff[i] -= sb;
-        if (doff) doff[i] -= db;
-    }
-}
-
-// Exclusive prefix sum of v[i] (0 where rc[i] != 0, if rc is given) into out[]; kScanBlock values per
-// block, block totals to bsum[] (scan_blocks_kernel turns them into block bases, bsum[nb] = total).
-constexpr uint32_t kScanBlock = 1024;
-static_assert(kScanBlock == kIdxScanBlock, "the chunk pass sizes scan_u32's block sums");
-__global__ __launch_bounds__(kScanBlock) void scan_local_kernel(const uint32_t *v, const int32_t *rc, uint32_t n,
-                                                                 uint64_t *out, uint64_t *bsum) {
-    __shared__ uint64_t s[kScanBlock];
-    const uint32_t t = threadIdx.x, i = blockIdx.x * kScanBlock + t;
-    const uint64_t x = i < n && !(rc && rc[i] != 0) ? v[i] : 0;
-    s[t] = x;
-    __syncthreads();
-    for (uint32_t d = 1; d < kScanBlock; d <<= 1) {
-        uint64_t y = t >= d ? s[t - d] : 0;
-        __syncthreads();
-        s[t] += y;
-        __syncthreads();
-    }
-    if (i < n) out[i] = s[t] - x;
-    if (t == kScanBlock - 1) bsum[blockIdx.x] = s[t];
-}
-
-__global__ __launch_bounds__(kScanBlock) void scan_blocks_kernel(uint64_t *bsum, uint32_t nb) {
-    __shared__ uint64_t s[kScanBlock];
-    __shared__ uint64_t carry;
-    const uint32_t t = threadIdx.x;
-    if (t == 0) carry = 0;
-    __syncthreads();
-    for (uint32_t base = 0; base < nb; base += kScanBlock) {
-        const uint64_t x = base + t < nb ? bsum[base + t] : 0;
-        s[t] = x;
-        __syncthreads();
-        for (uint32_t d = 1; d < kScanBlock; d <<= 1) {
-            uint64_t y = t >= d ? s[t - d] : 0;
-            __syncthreads();
-            s[t] += y;
-            __syncthreads();
-        }
-        if (base + t < nb) bsum[base + t] = carry + s[t] - x;
-        __syncthreads();
-        if (t == kScanBlock - 1) carry += s[t];
-        __syncthreads();
-    }
-    if (t == 0) bsum[nb] = carry;
-}
-
-__global__ __launch_bounds__(kScanBlock) void scan_add_kernel(uint64_t *out, uint32_t n, const uint64_t *bsum) {
-    const uint32_t i = blockIdx.x * kScanBlock + threadIdx.x;
-    if (i < n) out[i] += bsum[blockIdx.x];
-}
-
-// One wave per member: slot bytes dst[doff[i] ..+ len[i]) -> packed[poff[i] ..) (rc[i] != 0: none).
-__global__ __launch_bounds__(256) void compact_kernel(const uint8_t *dst, const uint64_t *doff, const uint32_t *len,
-                                                      const int32_t *rc, const uint64_t *poff, uint32_t n,
-                                                      uint8_t *packed) {
-    const uint32_t lane = threadIdx.x & 63, waves = gridDim.x * (blockDim.x >> 6);
-    for (uint32_t i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); i < n; i += waves) {
-        if (rc[i] != 0) continue;
-        const uint8_t *a = dst + doff[i];
-        uint8_t *b = packed + poff[i];
-        for (uint32_t k = lane; k < len[i]; k += 64) b[k] = a[k];
-    }
-}
-
-int scan_u32(const uint32_t *v, const int32_t *rc, uint32_t n, uint64_t *out, uint64_t *bsum, hipStream_t st) {
-    const uint32_t nb = (n + kScanBlock - 1) / kScanBlock;
-    hipLaunchKernelGGL(scan_local_kernel, dim3(nb), dim3(kScanBlock), 0, st, v, rc, n, out, bsum);
-    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(kScanBlock), 0, st, bsum, nb);
-    hipLaunchKernelGGL(scan_add_kernel, dim3(nb), dim3(kScanBlock), 0, st, out, n, bsum);
-    HIP_TRY(hipGetLastError());
-    return PMC_OK;
-}
-
-int pipe_init(pmc_ctx *ctx) {
-    auto &P = ctx->pipe;
-    if (P.h2d) return PMC_OK;
-    HIP_TRY(hipStreamCreateWithFlags(&P.h2d, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&P.d2h, hipStreamNonBlocking));
-    for (int k = 0; k < 2; k++) {
-        HIP_TRY(hipEventCreateWithFlags(&P.in[k], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&P.out[k], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&P.done[k], hipEventDisableTiming));
-    }
-    return P.total.ensure(64);
-}
-
-// Pinned host batch, chunked and software-pipelined over three streams (s = c & 1):
-//   h2d:    offsets/lengths/caps of chunk c, then its source byte range  -> event in[s]
-//   stream: rebase offsets, the codec kernels                            -> event out[s]
-//   d2h:    dst_len, rc, then the chunk's destination bytes              -> event done[s]
-// and chunk c + 2 reuses slot s after done[s].  Chunk c's source bytes are the range
-// [min src_off, max src_off + src_len) of its values (packed layouts copy exactly their bytes).
-// Destinations, three ways:
-//   tiled slots (dst_off given, and the chunk's slots tile one range in index order:
-//     dst_off[i + 1] == dst_off[i] + dst_cap[i]): the range is copied back whole, straight into dst;
-//   any other slot layout (gaps, permuted or interleaved slots): the device compacts the chunk's
-//     outputs, they land in a pinned bounce buffer and the host copies each output to its dst_off,
-//     so no byte outside [dst_off[i], dst_off[i] + dst_len[i]) of a successful value is written;
-//   packed mode (dst_off null): the compacted bytes are appended to dst.
-// A compacted chunk's device slots are laid out by a scan of dst_cap, its results compacted by a
-// scan of dst_len (rc != 0 -> 0 bytes); the host waits for chunk c's byte total (on the compute
-// stream, after its kernels) only once chunk c + 1's kernels are enqueued, so the device never idles.
-int pinned_batch_run(pmc_ctx *ctx, Dir dir, const uint8_t *src, const uint64_t *src_off, const uint32_t *src_len,
-                     uint32_t n, uint8_t *dst, const uint64_t *dst_off, const uint32_t *dst_cap, uint32_t *dst_len,
-                     int32_t *rc, uint32_t max_len, uint32_t chunk) {
-    if (!ctx || !src || !src_off || !src_len || !dst || !dst_cap || !dst_len || !rc) return PMC_E_ARG;
-    if (n == 0) return PMC_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    int r = pipe_init(ctx);
-    if (r) return r;
-    auto &P = ctx->pipe;
-    const bool packed = dst_off == nullptr;
-    if (chunk == 0) chunk = std::max<uint32_t>(65536, (n + 15) / 16);
-    auto al = [](uint64_t x) { return (x + 255) & ~(uint64_t)255; };
-    const uint32_t nchunks = (uint32_t)((n + (uint64_t)chunk - 1) / chunk);
-    volatile uint64_t *h_total = (volatile uint64_t *)P.total.p;  // chunk totals, slot s at [s]
-    uint8_t *d_pk[2] = {nullptr, nullptr};
-    uint64_t out_pos = 0;
-    // slot mode, compacted chunk: its outputs wait in bounce[s] until done[s], then go to dst_off
-    struct Pend {
-        bool on = false;
-        uint32_t a = 0, m = 0;
-    } pend[2];
-    auto scatter = [&](uint32_t s) -> int {
-        if (!pend[s].on) return PMC_OK;
-        HIP_TRY(hipEventSynchronize(P.done[s]));
-        const uint8_t *b = (const uint8_t *)P.bounce[s].p;
-        uint64_t p = 0;
-        for (uint32_t i = pend[s].a; i < pend[s].a + pend[s].m; i++)
-            if (rc[i] == 0) {
-                memcpy(dst + dst_off[i], b + p, dst_len[i]);
-                p += dst_len[i];
-            }
-        pend[s].on = false;
-        return PMC_OK;
-    };
-    // compacted chunk c's bytes go back once its total is known (called after chunk c + 1 is enqueued)
-    auto finish = [&](uint32_t c) -> int {
-        const uint32_t s = c & 1;
-        HIP_TRY(hipEventSynchronize(P.out[s]));
-        const uint64_t tot = h_total[s];
-        uint8_t *to = dst + out_pos;
-        if (!packed) {
-            int e = scatter(s);  // chunk c - 2's outputs leave bounce[s] first
-            if (e) return e;
-            if ((e = P.bounce[s].ensure(tot + 64))) return e;
-            to = (uint8_t *)P.bounce[s].p;
-            pend[s].on = true;
-            pend[s].a = c * chunk;
-            pend[s].m = std::min<uint32_t>(chunk, n - c * chunk);
-        }
-        HIP_TRY(hipStreamWaitEvent(P.d2h, P.out[s], 0));
-        if (tot) HIP_TRY(hipMemcpyAsync(to, d_pk[s], tot, hipMemcpyDeviceToHost, P.d2h));
-        HIP_TRY(hipEventRecord(P.done[s], P.d2h));
-        if (packed) out_pos += tot;
-        return PMC_OK;
-    };
-    int64_t unfinished = -1;  // a compacted chunk whose D2H is not enqueued yet
-    for (uint32_t c = 0; c < nchunks; c++) {
-        const uint32_t a = c * chunk, m = std::min<uint32_t>(chunk, n - a), s = c & 1;
-        uint64_t sb = ~0ull, se = 0, db = ~0ull, de = 0;
-        for (uint32_t i = a; i < a + m; i++) {
-            sb = std::min(sb, src_off[i]);
-            se = std::max(se, src_off[i] + src_len[i]);
-        }
-        bool compact = packed;
-        if (!packed) {
-            for (uint32_t i = a; i + 1 < a + m && !compact; i++) compact = dst_off[i + 1] != dst_off[i] + dst_cap[i];
-            db = dst_off[a];
-            de = dst_off[a + m - 1] + dst_cap[a + m - 1];
-        }
-        if (compact) {
-            db = 0;
-            de = 0;
-            for (uint32_t i = a; i < a + m; i++) de += dst_cap[i];
-        }
-        const uint32_t nb = (m + kScanBlock - 1) / kScanBlock;
-        const uint64_t meta = al(m * 8ull) * 3 + al(m * 4ull) * 4 + al((nb + 1) * 8ull);
-        const uint64_t need = meta + al(se - sb + 16) + al(de - db + 16) * (compact ? 2 : 1);
-        if (need > P.slot[s].cap) {
-            // the slot's previous chunk must have drained before it is reallocated
-            if (P.busy[s]) HIP_TRY(hipEventSynchronize(P.done[s]));
-            r = P.slot[s].ensure(need + need / 8);
-            if (r) return r;
-            P.busy[s] = false;
-        }
-        uint8_t *dp = (uint8_t *)P.slot[s].p;
-        uint64_t *d_soff = (uint64_t *)dp, *d_doff = d_soff + al(m * 8ull) / 8, *d_poff = d_doff + al(m * 8ull) / 8;
-        uint32_t *d_slen = (uint32_t *)(d_poff + al(m * 8ull) / 8);
-        uint32_t *d_dcap = d_slen + al(m * 4ull) / 4, *d_dlen = d_dcap + al(m * 4ull) / 4;
-        int32_t *d_rc = (int32_t *)(d_dlen + al(m * 4ull) / 4);
-        uint64_t *d_bsum = (uint64_t *)(d_rc + al(m * 4ull) / 4);
-        uint8_t *d_src = dp + meta, *d_dst = d_src + al(se - sb + 16);
-        d_pk[s] = d_dst + al(de - db + 16);
-        if (P.busy[s]) HIP_TRY(hipStreamWaitEvent(P.h2d, P.done[s], 0));
-        HIP_TRY(hipMemcpyAsync(d_soff, src_off + a, m * 8ull, hipMemcpyHostToDevice, P.h2d));
-        if (!compact) HIP_TRY(hipMemcpyAsync(d_doff, dst_off + a, m * 8ull, hipMemcpyHostToDevice, P.h2d));
-        HIP_TRY(hipMemcpyAsync(d_slen, src_len + a, m * 4ull, hipMemcpyHostToDevice, P.h2d));
-        HIP_TRY(hipMemcpyAsync(d_dcap, dst_cap + a, m * 4ull, hipMemcpyHostToDevice, P.h2d));
-        HIP_TRY(hipMemcpyAsync(d_src, src + sb, se - sb, hipMemcpyHostToDevice, P.h2d));
-        HIP_TRY(hipEventRecord(P.in[s], P.h2d));
-        HIP_TRY(hipStreamWaitEvent(ctx->stream, P.in[s], 0));
-        hipLaunchKernelGGL(rebase_kernel, dim3(std::min<uint32_t>((m + 255) / 256, 1024)), dim3(256), 0, ctx->stream,
-                           d_soff, compact ? nullptr : d_doff, m, sb, db);
-        HIP_TRY(hipGetLastError());
-        if (compact && (r = scan_u32(d_dcap, nullptr, m, d_doff, d_bsum, ctx->stream))) return r;
-        r = dir == kCompress
-                ? pmc_gzip_compress_batch(ctx, d_src, d_soff, d_slen, m, d_dst, d_doff, d_dcap, d_dlen, d_rc,
-                                          max_len, ctx->stream)
-                : pmc_gzip_decompress_batch(ctx, d_src, d_soff, d_slen, m, d_dst, d_doff, d_dcap, d_dlen, d_rc,
-                                            max_len, ctx->stream);
-        if (r) return r;
-        if (compact) {
-            if ((r = scan_u32(d_dlen, d_rc, m, d_poff, d_bsum, ctx->stream))) return r;
-            hipLaunchKernelGGL(compact_kernel, dim3(std::min<uint32_t>((m + 3) / 4, 8192)), dim3(256), 0,
-                               ctx->stream, d_dst, d_doff, d_dlen, d_rc, d_poff, m, d_pk[s]);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(dst_len + a, d_dlen, m * 4ull, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(hipMemcpyAsync(rc + a, d_rc, m * 4ull, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(hipMemcpyAsync((void *)(h_total + s), d_bsum + nb, 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(hipEventRecord(P.out[s], ctx->stream));
-        } else {
-            HIP_TRY(hipEventRecord(P.out[s], ctx->stream));
-            HIP_TRY(hipStreamWaitEvent(P.d2h, P.out[s], 0));
-            HIP_TRY(hipMemcpyAsync(dst_len + a, d_dlen, m * 4ull, hipMemcpyDeviceToHost, P.d2h));
-            HIP_TRY(hipMemcpyAsync(rc + a, d_rc, m * 4ull, hipMemcpyDeviceToHost, P.d2h));
-            HIP_TRY(hipMemcpyAsync(dst + db, d_dst, de - db, hipMemcpyDeviceToHost, P.d2h));
-            HIP_TRY(hipEventRecord(P.done[s], P.d2h));
-        }
-        P.busy[s] = true;
-        if (unfinished >= 0 && (r = finish((uint32_t)unfinished))) return r;
-        unfinished = compact ? (int64_t)c : -1;
-    }
-    if (unfinished >= 0 && (r = finish((uint32_t)unfinished))) return r;
-    // slot mode: the last compacted chunks' outputs to their dst_off, in chunk order
-    for (uint32_t k = 0; k < 2; k++) {
-        const uint32_t s = nchunks >= 2 ? (nchunks - 2 + k) & 1 : k;
-        if ((r = scatter(s))) return r;
-    }
-    HIP_TRY(hipStreamSynchronize(P.d2h));
-    P.busy[0] = P.busy[1] = false;
-    return PMC_OK;
-}
-
-// On an error part of the batch may still be in flight on the three streams, reading and writing the
-// caller's buffers: drain them before returning, so the caller may free those buffers at once.
-int pinned_batch(pmc_ctx *ctx, Dir dir, const uint8_t *src, const uint64_t *src_off, const uint32_t *src_len,
-                 uint32_t n, uint8_t *dst, const uint64_t *dst_off, const uint32_t *dst_cap, uint32_t *dst_len,
-                 int32_t *rc, uint32_t max_len, uint32_t chunk) {
-    if (!ctx) return PMC_E_ARG;
-    HostCall guard(ctx);
-    const int r = pinned_batch_run(ctx, dir, src, src_off, src_len, n, dst, dst_off, dst_cap, dst_len, rc, max_len,
-                                   chunk);
-    if (r && ctx && ctx->pipe.h2d) {
-        (void)hipStreamSynchronize(ctx->pipe.h2d);
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipStreamSynchronize(ctx->pipe.d2h);
-        ctx->pipe.busy[0] = ctx->pipe.busy[1] = false;
-    }
-    return r;
-}
-
-} // namespace
-
-PMC_API int pmc_gzip_compress_batch_host(pmc_ctx *ctx, const uint8_t *src, const uint64_t *src_off,
-                                         const uint32_t *src_len, uint32_t n, uint8_t *dst, const uint64_t *dst_off,
-                                         const uint32_t *dst_cap, uint32_t *dst_len, int32_t *rc) {
-    return host_batch(ctx, kCompress, src, src_off, src_len, n, dst, dst_off, dst_cap, dst_len, rc);
-}
-
-PMC_API int pmc_gzip_decompress_batch_host(pmc_ctx *ctx, const uint8_t *src, const uint64_t *src_off,
-                                           const uint32_t *src_len, uint32_t n, uint8_t *dst,
-                                           const uint64_t *dst_off, const uint32_t *dst_cap, uint32_t *dst_len,
-                                           int32_t *rc) {
-    return host_batch(ctx, kDecompress, src, src_off, src_len, n, dst, dst_off, dst_cap, dst_len, rc);
-}
-
-PMC_API int pmc_gzip_compress_batch_pinned(pmc_ctx *ctx, const uint8_t *src, const uint64_t *src_off,
-                                           const uint32_t *src_len, uint32_t n, uint8_t *dst,
-                                           const uint64_t *dst_off, const uint32_t *dst_cap, uint32_t *dst_len,
-                                           int32_t *rc, uint32_t max_len, uint32_t chunk) {
-    return pinned_batch(ctx, kCompress, src, src_off, src_len, n, dst, dst_off, dst_cap, dst_len, rc, max_len,
-                        chunk);
-}
-
-PMC_API int pmc_gzip_decompress_batch_pinned(pmc_ctx *ctx, const uint8_t *src, const uint64_t *src_off,
-                                             const uint32_t *src_len, uint32_t n, uint8_t *dst,
-                                             const uint64_t *dst_off, const uint32_t *dst_cap, uint32_t *dst_len,
-                                             int32_t *rc, uint32_t max_len, uint32_t chunk) {
-    return pinned_batch(ctx, kDecompress, src, src_off, src_len, n, dst, dst_off, dst_cap, dst_len, rc, max_len,
-                        chunk);
-}
-
-PMC_API int pmc_gzip_compress(pmc_ctx *ctx, const void *in, size_t in_len, void *out, size_t out_cap,
-                              size_t *out_len) {
-    *out_len = 0;
-    if (!in || in_len == 0) return PMC_INVALID_INPUT;
-    if (!ctx) ctx = pmc_default_ctx();
-    if (!ctx) return PMC_E_NO_DEVICE;
-    if (in_len > 0xffffffffull || out_cap < pmc_gzip_bound(in_len)) return PMC_E_CAPACITY;
-    uint64_t so = 0;
-    uint32_t sl = (uint32_t)in_len, cap = (uint32_t)std::min<size_t>(out_cap, 0xffffffffull), dl = 0;
-    int32_t rc = 0;
-    int r = host_batch(ctx, kCompress, (const uint8_t *)in, &so, &sl, 1, (uint8_t *)out, &so, &cap, &dl, &rc);
-    if (r) return r;
-    *out_len = dl;
-    return rc;
-}
-
-PMC_API int pmc_gzip_decompress(pmc_ctx *ctx, const void *in, size_t in_len, void *out, size_t out_cap,
-                                size_t *out_len) {
-    *out_len = 0;
-    if (!in || in_len == 0) return PMC_INVALID_INPUT;
-    if (!ctx) ctx = pmc_default_ctx();
-    if (!ctx) return PMC_E_NO_DEVICE;
-    uint64_t so = 0;
-    uint32_t sl = (uint32_t)in_len, cap = (uint32_t)std::min<size_t>(out_cap, 0xffffffffull), dl = 0;
-    int32_t rc = 0;
-    int r = host_batch(ctx, kDecompress, (const uint8_t *)in, &so, &sl, 1, (uint8_t *)out, &so, &cap, &dl, &rc);
-    if (r) return r;
-    *out_len = dl;
-    return rc;
 }
 
 // ---- helpers -------------------------------------------------------------------------

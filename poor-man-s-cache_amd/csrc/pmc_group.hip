@@ -5,7 +5,7 @@
 // s % nGPU, so a host batch is split by that route, each GPU's share goes through its own context
 // (pinned staging, copy streams, kernels) on its own host thread, and the results are put back in
 // the caller's order.  No data crosses between GPUs: there is no collective.  Compiled into the
-// unity TU after pmc_capi.hip (host code only).
+// unity TU after pmc_host.hip (its pinned_batch; host code only).
 
 #include <thread>
 

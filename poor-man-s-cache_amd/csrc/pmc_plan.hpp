@@ -1,10 +1,13 @@
 // pmc_plan.hpp -- the host-side planning arithmetic of a compress call: which path claims which lengths
 // (Route), where the split pipeline's chunk arrays lie (SplitLayout) and how the large values are cut
 // into rounds (LvRound); and of a decompress call: which route it takes (inflate_latency), which stages
-// run and every grid, group and scratch size of them (InflatePlan).  Plain C++17 with no HIP in it:
-// pmc_capi.hip turns these plans into launches, and tests/host/plan_check.cpp prints them for
-// tests/test_host_plan.py, which needs no GPU.
+// run and every grid, group and scratch size of them (InflatePlan); and of a host-memory call: where the
+// arrays of its staging lie (StageCarver, HostStage, PinnedSlot), which route it takes (plan_host_batch) and
+// what a pinned call's chunks cover (plan_pinned_chunk).  Plain C++17 with no HIP in it: pmc_capi.hip and
+// pmc_host.hip turn these plans into launches, and tests/host/plan_check.cpp prints them for
+// tests/test_host_plan.py and tests/test_host_batch_plan.py, which need no GPU.
 #pragma once
+#include <assert.h>
 #include <stdint.h>
 
 #include <algorithm>
@@ -854,5 +857,186 @@ inline InflatePlan plan_inflate(const InflateIn &in) {
     P.second.first_in = (uint32_t)P.lds_max_in;
     return P;
 }
+
+// ---- staging layouts ---------------------------------------------------------------------------------------
+// A call's staging is one pinned host buffer and one device buffer of the same layout: arrays of m elements,
+// each starting on a multiple of 256 bytes, then the call's bytes from `meta` on.  The host side is filled and
+// copied over in one piece.  An array knows its offset, its host pointer (from the host base) and its device
+// pointer (from the device base).
+inline uint64_t al256(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
+template <class T>
+struct StageArr {
+    uint64_t off;
+    T *h, *d;
+};
+// two arrays that one copy fetches: `bytes` from the first one's start
+struct StageSpan {
+    void *h, *d;
+    uint64_t bytes;
+};
+// Hands out the arrays in declaration order.  (Without bases -- to learn `meta` before the buffers are
+// sized -- the pointers are the offsets.)
+struct StageCarver {
+    uint64_t m, meta = 0;
+    uintptr_t hp, dp;
+    explicit StageCarver(uint64_t m, void *host = nullptr, void *dev = nullptr)
+        : m(m), hp((uintptr_t)host), dp((uintptr_t)dev) {}
+    // a run of `count` elements between the arrays: raw bytes, or an array of another length than m
+    template <class T = uint8_t>
+    StageArr<T> run(uint64_t count) {
+        const StageArr<T> a{meta, (T *)(hp + meta), (T *)(dp + meta)};
+        meta += al256(count * sizeof(T));
+        return a;
+    }
+    template <class T>
+    StageArr<T> take() {
+        return run<T>(m);
+    }
+    StageArr<uint64_t> u64() { return take<uint64_t>(); }
+    StageArr<uint32_t> u32() { return take<uint32_t>(); }
+    StageArr<int32_t> i32() { return take<int32_t>(); }
+    // a's and b's bytes as one span: b lies directly behind a
+    template <class A, class B>
+    StageSpan span(const StageArr<A> &a, const StageArr<B> &b) const {
+        assert(a.off + al256(m * sizeof(A)) == b.off);
+        return StageSpan{a.h, a.d, al256(m * sizeof(A)) + al256(m * sizeof(B))};
+    }
+};
+// A layout of arrays alone, one per call site (members are initialised in declaration order: that order is
+// the layout).  pmc_store_plan.hpp states the store's with it.
+#define PMC_STAGE(Name)                                                                            \
+    explicit Name(uint64_t m, void *host = nullptr, void *dev = nullptr) : c(m, host, dev) {} \
+    StageCarver c
+
+// ---- a host-memory call (pmc_host.hip: pmc_gzip_*_batch_host, pmc_gzip_compress / _decompress) --------------
+// Its staging, in the order of the two copies: [offsets, lengths, caps | source bytes] go down in one H2D of
+// `down` bytes, [output lengths, verdicts | output bytes] come back in one D2H of `up` bytes from dlen on.
+struct HostStage {
+    HostStage(uint64_t n, uint64_t in_bytes, uint64_t out_bytes, void *host = nullptr, void *dev = nullptr)
+        : c(n, host, dev), in_bytes(in_bytes), out_bytes(out_bytes) {}
+    StageCarver c;
+    uint64_t in_bytes, out_bytes;
+    StageArr<uint64_t> soff = c.u64(), doff = c.u64();
+    StageArr<uint32_t> slen = c.u32(), dcap = c.u32();
+    StageArr<uint8_t> src = c.run(in_bytes + 16);
+    uint64_t down = c.meta;
+    StageArr<uint32_t> dlen = c.u32();
+    StageArr<int32_t> rc = c.i32();
+    StageArr<uint8_t> dst = c.run(out_bytes + 16);
+    uint64_t up = c.meta - down;
+    uint64_t bytes() const { return down + up; }
+
+    // the host arrays of n values packed back to back: source i at the sum of the lengths before it, slot i
+    // at the sum of the capacities before it
+    void fill(const uint32_t *src_len, const uint32_t *dst_cap) const {
+        uint64_t so = 0, dof = 0;
+        for (uint64_t i = 0; i < c.m; i++) {
+            soff.h[i] = so;
+            slen.h[i] = src_len[i];
+            so += src_len[i];
+            doff.h[i] = dof;
+            dcap.h[i] = dst_cap[i];
+            dof += dst_cap[i];
+        }
+    }
+};
+
+struct HostBatchIn {
+    bool compress;
+    uint32_t n;
+    const uint32_t *src_len, *dst_cap;
+    uint64_t cus;
+    bool level_fast, lane_order_ok; // level_is_fast of the context's level; its lane-order probe passed
+    // latency_batch(), latency_max_len() and the LDS wave kernel's output image (kInflateLdsOut)
+    uint64_t lat_batch, lat_max_len, out_limit;
+    bool force_pipeline;            // the throughput route whatever the batch's size
+};
+struct HostBatchPlan {
+    uint64_t in_bytes, out_bytes; // the sums of src_len and of dst_cap
+    uint64_t max_len, max_in;     // the largest source length (decompress: capacity); the largest source length
+    bool latency;                 // the one-kernel route, in coherent host memory and without copies
+    bool need_hbm;                // decompress: inflate_need_hbm (compress: unused, false)
+    int path;                     // the pmc_ctx_path_counts counter of this call
+};
+// Routing (limits measured with scripts/few_sweep.py).  Compress: up to 1,024 values of <= 4 KiB the
+// one-kernel path (deflate_small_kernel) beats the pipeline; above 4 KiB the wave-per-value kernel would
+// work from HBM, far slower than the split pipeline's large pass; a fast level always takes the pipeline
+// (the one-kernel path is exact only).  Decompress: the wave-per-member inflate kernel holds a member's
+// output in LDS up to out_limit (48 KiB), so a member up to that size stays on the latency path (a 30 KB
+// member: 0.81 ms there against 3.8 ms through the pipeline); its batch limit is 4,096
+// members / 16 MiB of output (inflate_latency: round 5 measured the wave kernel still 2x ahead there).
+inline HostBatchPlan plan_host_batch(const HostBatchIn &in) {
+    HostBatchPlan P{};
+    for (uint32_t i = 0; i < in.n; i++) {
+        P.in_bytes += in.src_len[i];
+        P.out_bytes += in.dst_cap[i];
+        P.max_len = std::max<uint64_t>(P.max_len, in.compress ? in.src_len[i] : in.dst_cap[i]);
+        P.max_in = std::max<uint64_t>(P.max_in, in.src_len[i]);
+    }
+    const bool fast = in.compress && in.level_fast && in.lane_order_ok;
+    P.latency = !in.force_pipeline &&
+                (in.compress ? !fast && in.n <= in.lat_batch && P.max_len <= in.lat_max_len
+                             : inflate_latency(in.n, P.max_len, P.out_bytes, in.cus, in.lat_batch, in.lat_max_len, false,
+                                               in.out_limit));
+    // the wave kernels' HBM variant only for members the LDS image cannot hold
+    P.need_hbm = !in.compress && inflate_need_hbm(P.latency, P.max_len, P.max_in, in.out_limit);
+    P.path = (P.latency ? 0 : 2) + (in.compress ? 0 : 1);
+    return P;
+}
+
+// ---- a pinned call's chunks (pmc_host.hip: pmc_gzip_*_batch_pinned) -----------------------------------------
+constexpr uint32_t kIdxScanBlock = 1024; // (= kScanBlock: scan_u32's block sums, one per so many members)
+
+// values per chunk (the caller's, or by default a sixteenth of the batch and at least 65,536) and chunks
+struct PinnedChunks {
+    uint32_t chunk, nchunks;
+};
+inline PinnedChunks pinned_chunk_of(uint32_t n, uint32_t chunk) {
+    if (chunk == 0) chunk = std::max<uint32_t>(65536, (uint32_t)(((uint64_t)n + 15) / 16));
+    return PinnedChunks{chunk, (uint32_t)((n + (uint64_t)chunk - 1) / chunk)};
+}
+
+// What the chunk of values [a, a + m) covers (m >= 1).  Source: the range [sb, se) = [min src_off, max src_off +
+// src_len) of its values.  Destination [db, de): tiled slots (dst_off given, dst_off[i + 1] == dst_off[i] +
+// dst_cap[i] throughout the chunk) are that range of dst, copied back whole; any other slot layout, and packed
+// mode (dst_off null), is compacted: the device lays the slots out back to back from 0 by a scan of dst_cap.
+struct PinnedChunk {
+    uint64_t sb, se, db, de;
+    bool compact;
+    uint32_t nb; // scan_u32's blocks over the chunk
+};
+inline PinnedChunk plan_pinned_chunk(const uint64_t *src_off, const uint32_t *src_len, const uint64_t *dst_off,
+                                     const uint32_t *dst_cap, uint32_t a, uint32_t m) {
+    PinnedChunk k{~0ull, 0, 0, 0, dst_off == nullptr, (m + kIdxScanBlock - 1) / kIdxScanBlock};
+    const uint64_t end = (uint64_t)a + m;
+    for (uint64_t i = a; i < end; i++) {
+        k.sb = std::min(k.sb, src_off[i]);
+        k.se = std::max(k.se, src_off[i] + src_len[i]);
+    }
+    for (uint64_t i = a; i + 1 < end && !k.compact; i++) k.compact = dst_off[i + 1] != dst_off[i] + dst_cap[i];
+    if (k.compact) {
+        for (uint64_t i = a; i < end; i++) k.de += dst_cap[i];
+    } else {
+        k.db = dst_off[a];
+        k.de = dst_off[end - 1] + dst_cap[end - 1];
+    }
+    return k;
+}
+
+// A chunk's device slot: its arrays, scan_u32's block sums (the chunk's byte total behind them), its source
+// range, its slots and -- a compacted chunk only -- its outputs back to back, as large as the slots.
+struct PinnedSlot {
+    PinnedSlot(uint64_t m, const PinnedChunk &k, void *dev = nullptr) : c(m, nullptr, dev), k(k) {}
+    StageCarver c;
+    PinnedChunk k;
+    StageArr<uint64_t> soff = c.u64(), doff = c.u64(), poff = c.u64();
+    StageArr<uint32_t> slen = c.u32(), dcap = c.u32(), dlen = c.u32();
+    StageArr<int32_t> rc = c.i32();
+    StageArr<uint64_t> bsum = c.run<uint64_t>(k.nb + 1ull);
+    uint64_t meta = c.meta;
+    StageArr<uint8_t> src = c.run(k.se - k.sb + 16), dst = c.run(k.de - k.db + 16);
+    StageArr<uint8_t> packed = c.run(k.compact ? k.de - k.db + 16 : 0);
+    uint64_t need = c.meta;
+};
 
 } // namespace pmc

@@ -14,7 +14,7 @@
 // of a power of two above 8 KiB), per-size free lists, bump allocation otherwise.  A put compresses
 // into gzip_bound slots of its device staging, learns the lengths, allocates, then compacts.
 // Everything here that is arithmetic -- the allocator, the staging layouts, the framing, the fallback
-// rounds -- is pmc_store_plan.hpp's.  Compiled into the unity TU after pmc_capi.hip (uses pmc_ctx,
+// rounds -- is pmc_store_plan.hpp's.  Compiled into the unity TU after pmc_capi.hip and pmc_host.hip (uses pmc_ctx,
 // DevBuf, HostBuf, the scan/compact kernels).
 
 #include "pmc_store_plan.hpp"

@@ -1,19 +1,16 @@
 // pmc_store_plan.hpp -- the host-side arithmetic of the device store and the group calls: the heap allocator
-// (StoreHeap), where the arrays of every call's staging lie (StageCarver and the named layouts), the wire
+// (StoreHeap), where the arrays of every call's staging lie (the named layouts over pmc_plan.hpp's StageCarver), the wire
 // framing of a response (frame_head / frame_tail / frame_write) and how the values a ranged call read whole are
 // cut into rounds (cut_round).  Plain C++17 with no HIP in it: pmc_store.hip and pmc_group.hip turn these into
 // copies and launches, and tests/host/store_check.cpp prints them for tests/test_host_store.py, which needs
 // no GPU.
 #pragma once
-#include <assert.h>
-
 #include <unordered_map>
 
 #include "pmc_plan.hpp"
 
 namespace pmc {
 
-inline uint64_t al256(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
 inline uint64_t round16(uint64_t x) { return (x + 15) & ~(uint64_t)15; }
 
 // ---- the heap allocator ------------------------------------------------------------------------------------
@@ -59,48 +56,8 @@ struct StoreHeap {
 };
 
 // ---- staging layouts ---------------------------------------------------------------------------------------
-// A call's staging is one pinned host buffer and one device buffer of the same layout: arrays of m elements,
-// each starting on a multiple of 256 bytes, then the call's bytes from `meta` on.  The host side is filled and
-// copied over in one piece.  An array knows its offset, its host pointer (from the host base) and its device
-// pointer (from the device base).
-template <class T>
-struct StageArr {
-    uint64_t off;
-    T *h, *d;
-};
-// two arrays that one copy fetches: `bytes` from the first one's start
-struct StageSpan {
-    void *h, *d;
-    uint64_t bytes;
-};
-// Hands out the arrays in declaration order.  (Without bases -- to learn `meta` before the buffers are
-// sized -- the pointers are the offsets.)
-struct StageCarver {
-    uint64_t m, meta = 0;
-    uintptr_t hp, dp;
-    explicit StageCarver(uint64_t m, void *host = nullptr, void *dev = nullptr)
-        : m(m), hp((uintptr_t)host), dp((uintptr_t)dev) {}
-    template <class T>
-    StageArr<T> take() {
-        const StageArr<T> a{meta, (T *)(hp + meta), (T *)(dp + meta)};
-        meta += al256(m * sizeof(T));
-        return a;
-    }
-    StageArr<uint64_t> u64() { return take<uint64_t>(); }
-    StageArr<uint32_t> u32() { return take<uint32_t>(); }
-    StageArr<int32_t> i32() { return take<int32_t>(); }
-    // a's and b's bytes as one span: b lies directly behind a
-    template <class A, class B>
-    StageSpan span(const StageArr<A> &a, const StageArr<B> &b) const {
-        assert(a.off + al256(m * sizeof(A)) == b.off);
-        return StageSpan{a.h, a.d, al256(m * sizeof(A)) + al256(m * sizeof(B))};
-    }
-};
-
-// The layouts, one per call site (members are initialised in declaration order: that order is the layout).
-#define PMC_STAGE(Name)                                                                            \
-    explicit Name(uint64_t m, void *host = nullptr, void *dev = nullptr) : c(m, host, dev) {} \
-    StageCarver c
+// The store's layouts over pmc_plan.hpp's StageCarver, one per call site (members are initialised in declaration
+// order: that order is the layout).
 struct PutStage { // pmc_store_put_batch: ... | value bytes | member slots
     PMC_STAGE(PutStage);
     StageArr<uint64_t> soff = c.u64(), doff = c.u64(), poff = c.u64();

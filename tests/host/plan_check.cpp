@@ -11,6 +11,8 @@
 //                                           as integers), one JSON object per line
 //   plan_check latency                      inflate_latency of each input line (its arguments in order): 0 or 1
 //   plan_check need_hbm                     inflate_need_hbm of each input line (its arguments in order): 0 or 1
+//   plan_check host                         the plan and the HostStage of one host-memory call per input line
+//   plan_check pinned                       pinned_chunk_of, or the plan and the PinnedSlot of one chunk, per input line
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
@@ -126,6 +128,92 @@ static int inflate() {
     return 0;
 }
 
+// every integer of a line
+static std::vector<uint64_t> all_ints(const std::string &line) {
+    std::vector<uint64_t> v;
+    for (const char *p = line.c_str();;) {
+        char *e;
+        const uint64_t x = strtoull(p, &e, 10);
+        if (e == p) return v;
+        v.push_back(x);
+        p = e;
+    }
+}
+
+// compress level lane_order_ok force_pipeline cus lat_batch lat_max_len out_limit, then runs of values as
+// count src_len dst_cap
+static int host() {
+    char buf[1 << 16];
+    while (fgets(buf, sizeof buf, stdin)) {
+        const std::vector<uint64_t> v = all_ints(buf);
+        if (v.size() < 11 || (v.size() - 8) % 3) return 2;
+        std::vector<uint32_t> slen, dcap;
+        for (size_t k = 8; k < v.size(); k += 3) {
+            slen.insert(slen.end(), v[k], (uint32_t)v[k + 1]);
+            dcap.insert(dcap.end(), v[k], (uint32_t)v[k + 2]);
+        }
+        const uint32_t n = (uint32_t)slen.size();
+        const HostBatchPlan p = plan_host_batch({v[0] != 0, n, slen.data(), dcap.data(), v[4], level_is_fast((int)v[1]),
+                                                 v[2] != 0, v[5], v[6], v[7], v[3] != 0});
+        const HostStage L(n, p.in_bytes, p.out_bytes);
+        printf("{\"in_bytes\":%" PRIu64 ",\"out_bytes\":%" PRIu64 ",\"max_len\":%" PRIu64 ",\"max_in\":%" PRIu64
+               ",\"latency\":%d,\"need_hbm\":%d,\"path\":%d",
+               p.in_bytes, p.out_bytes, p.max_len, p.max_in, (int)p.latency, (int)p.need_hbm, p.path);
+        printf(",\"soff\":%" PRIu64 ",\"doff\":%" PRIu64 ",\"slen\":%" PRIu64 ",\"dcap\":%" PRIu64 ",\"src\":%" PRIu64
+               ",\"dlen\":%" PRIu64 ",\"rc\":%" PRIu64 ",\"dst\":%" PRIu64 ",\"down\":%" PRIu64 ",\"up\":%" PRIu64
+               ",\"bytes\":%" PRIu64,
+               L.soff.off, L.doff.off, L.slen.off, L.dcap.off, L.src.off, L.dlen.off, L.rc.off, L.dst.off, L.down, L.up,
+               L.bytes());
+        // the arrays HostStage::fill writes (it touches nothing behind them, so a buffer up to `src` will do)
+        std::vector<uint64_t> image(L.src.off / 8);
+        const HostStage F(n, p.in_bytes, p.out_bytes, image.data());
+        F.fill(slen.data(), dcap.data());
+        bool same = true;
+        for (uint32_t i = 0; i < n; i++) same = same && F.slen.h[i] == slen[i] && F.dcap.h[i] == dcap[i];
+        printf(",\"lens_copied\":%d,\"soff_v\":[", (int)same);
+        for (uint32_t i = 0; i < n && i < 8; i++) printf("%s%" PRIu64, i ? "," : "", F.soff.h[i]);
+        printf("],\"doff_v\":[");
+        for (uint32_t i = 0; i < n && i < 8; i++) printf("%s%" PRIu64, i ? "," : "", F.doff.h[i]);
+        printf("],\"soff_last\":%" PRIu64 ",\"doff_last\":%" PRIu64 "}\n", F.soff.h[n - 1], F.doff.h[n - 1]);
+    }
+    return 0;
+}
+
+// "n chunk": pinned_chunk_of; "packed a m", then src_off src_len dst_off dst_cap of every value of the batch:
+// the plan and the device slot of the chunk [a, a + m)
+static int pinned() {
+    static char buf[1 << 20];
+    while (fgets(buf, sizeof buf, stdin)) {
+        const std::vector<uint64_t> v = all_ints(buf);
+        if (v.size() == 2) {
+            const PinnedChunks c = pinned_chunk_of((uint32_t)v[0], (uint32_t)v[1]);
+            printf("{\"chunk\":%u,\"nchunks\":%u}\n", c.chunk, c.nchunks);
+            continue;
+        }
+        if (v.size() < 7 || (v.size() - 3) % 4) return 2;
+        std::vector<uint64_t> soff, doff;
+        std::vector<uint32_t> slen, dcap;
+        for (size_t k = 3; k < v.size(); k += 4) {
+            soff.push_back(v[k]);
+            slen.push_back((uint32_t)v[k + 1]);
+            doff.push_back(v[k + 2]);
+            dcap.push_back((uint32_t)v[k + 3]);
+        }
+        const uint32_t a = (uint32_t)v[1], m = (uint32_t)v[2];
+        if (m == 0 || (uint64_t)a + m > soff.size()) return 2;
+        const PinnedChunk k = plan_pinned_chunk(soff.data(), slen.data(), v[0] ? nullptr : doff.data(), dcap.data(), a, m);
+        const PinnedSlot L(m, k);
+        printf("{\"sb\":%" PRIu64 ",\"se\":%" PRIu64 ",\"db\":%" PRIu64 ",\"de\":%" PRIu64 ",\"compact\":%d,\"nb\":%u", k.sb,
+               k.se, k.db, k.de, (int)k.compact, k.nb);
+        printf(",\"soff\":%" PRIu64 ",\"doff\":%" PRIu64 ",\"poff\":%" PRIu64 ",\"slen\":%" PRIu64 ",\"dcap\":%" PRIu64
+               ",\"dlen\":%" PRIu64 ",\"rc\":%" PRIu64 ",\"bsum\":%" PRIu64 ",\"meta\":%" PRIu64 ",\"src\":%" PRIu64
+               ",\"dst\":%" PRIu64 ",\"packed\":%" PRIu64 ",\"need\":%" PRIu64 "}\n",
+               L.soff.off, L.doff.off, L.poff.off, L.slen.off, L.dcap.off, L.dlen.off, L.rc.off, L.bsum.off, L.meta,
+               L.src.off, L.dst.off, L.packed.off, L.need);
+    }
+    return 0;
+}
+
 // inflate_latency (8 arguments) or inflate_need_hbm (4) of each input line
 static int predicate(int nargs) {
     char line[512];
@@ -152,6 +240,8 @@ int main(int argc, char **argv) {
     if (argc == 2 && !strcmp(argv[1], "inflate")) return inflate();
     if (argc == 2 && !strcmp(argv[1], "latency")) return predicate(8);
     if (argc == 2 && !strcmp(argv[1], "need_hbm")) return predicate(4);
-    fprintf(stderr, "usage: plan_check lv|layout|chunk|route|inflate|latency|need_hbm ...\n");
+    if (argc == 2 && !strcmp(argv[1], "host")) return host();
+    if (argc == 2 && !strcmp(argv[1], "pinned")) return pinned();
+    fprintf(stderr, "usage: plan_check lv|layout|chunk|route|inflate|latency|need_hbm|host|pinned ...\n");
     return 2;
 }

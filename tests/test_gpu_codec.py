@@ -651,7 +651,7 @@ def test_multi_megabyte_values_vs_oracle(ctx, D, golden, large_golden):
 @pytest.mark.parametrize("dig", [0, 1, 2, 3], ids=["256B", "1KiB", "4KiB", "1KiB-alnum"])
 def test_latency_path_batches_vs_reference(ctx, golden, dig):
     """host calls of 1, 64, 400 and 1,024 values of 256 B / 1 KiB / 4 KiB take the latency
-    path (one wave-per-value kernel over coherent host memory, pmc_capi.hip host_batch) -- asserted through
+    path (one wave-per-value kernel over coherent host memory, pmc_host.hip host_batch) -- asserted through
     the context's route counters -- and their members are the reference's: the calls cover a whole digest
     set of tests/golden/golden_index.json (the reference's own Compress over the same generator), whose
     SHA-256 over the concatenated members and over their sizes must match.  Then the members come back

@@ -116,7 +116,7 @@ def _run_host(lib):
 @pytest.mark.gpu
 def test_latency_path_declined_values_redone_through_the_pipeline():
     """the latency path (host calls, one wave-per-value kernel) has no retry pass; values it
-    declines are redone alone by a pipeline call (pmc_capi.hip host_batch_locked).  Under the fault build
+    declines are redone alone by a pipeline call (pmc_host.hip host_batch_locked).  Under the fault build
     its guards decline values on purpose: every member must still be the reference's, the calls must
     have taken the latency route AND the pipeline route, and the product library must never need it."""
     if not os.path.exists(os.path.join(PKG, "libpmc_codec_fault.so")):
