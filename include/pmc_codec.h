@@ -430,6 +430,58 @@ int pmc_gzip_grow_range_batch(pmc_ctx *ctx, const uint8_t *src, const uint64_t *
 #define PMC_DICT_MAX 8192
 int pmc_ctx_set_dictionary(pmc_ctx *ctx, const void *dict, size_t len);
 int pmc_ctx_get_dictionary_id(pmc_ctx *ctx, uint32_t *id);
+
+/* ---- dictionary training ----------------------------------------------------------------------
+ * Makes a dictionary for pmc_ctx_set_dictionary (or for the file PMC_DICT names) from a batch of sample values.
+ * The algorithm is this library's own, a simplified FASTCOVER, and aims at byte parity with no other tool; its
+ * normative statement is tests/dict_train_model.py, and the result is a pure function of the samples, their order
+ * and dict_size -- so a dictionary can be made again and its id (the CRC-32 of its bytes) checked.
+ *
+ * Constants: d = 8 (bytes hashed per position), K = 64 (bytes per segment), F = 20 (the table has 2^F slots),
+ * W = K - d + 1 = 57 (positions per segment).  Inputs: samples v_0 .. v_{n-1}, 1 <= n <=
+ * PMC_DICT_TRAIN_MAX_SAMPLES, and dict_size D, a multiple of 64 with 64 <= D <= 8192.  A sample longer than 16382
+ * bytes counts as its first 16382 bytes only (the span in which a dictionary is ever used); 262144 * 16382 < 2^32,
+ * so no counter wraps.
+ *   HASH.  For position p of a sample with p + 8 <= len: w = the 8 bytes at p as a little-endian u64, and
+ *     h(p) = (w * 0x9E3779B185EBCA87 mod 2^64) >> 44.
+ *   COUNT.  freq[h(p)] += 1 for every such position of every sample, in u32.
+ *   EPOCHS.  E = D / 64.  Epoch e owns the samples with index in [e n / E, (e + 1) n / E) (integer division; the
+ *     range may be empty when n < E).  Epochs run in order e = 0 .. E - 1, each on the table as the earlier ones
+ *     left it.
+ *   SCORE.  In its epoch every sample i and start q with q + 64 <= len_i is a candidate segment, with the u64
+ *     score(i, q) = sum over j = 0 .. 56 of freq[h(i, q + j)], where a hash value counts once per window, at its
+ *     first position in the window (the term of j is dropped when some j' < j has h(i, q + j') == h(i, q + j)).
+ *   SELECTION.  The epoch takes the candidate with the largest score; ties go to the lowest i, then the lowest q.
+ *     An epoch with no candidate, or whose best score is 0, selects nothing.  When a segment is selected,
+ *     freq[h(i, q + j)] = 0 for j = 0 .. 56, and its 64 bytes become s_m, m counting the selections from 0.
+ *   ASSEMBLY.  The dictionary is s_{m-1} || .. || s_1 || s_0, 64 m <= D bytes: the first and best segment lies
+ *     last, next to the value, where distances are shortest.  m may be smaller than E, and it may be 0.
+ *
+ * pmc_dict_train_batch: every array is a device pointer, dict_len included; sample i is src[src_off[i] ..
+ * src_off[i] + src_len[i]), offsets may be unaligned, samples may overlap, and no byte outside a sample is looked
+ * at for its value.  The call only enqueues, on `stream` -- a fixed sequence of launches with no read-back -- and
+ * is ordered with the context's compress-direction calls, whose lock and event it shares.
+ * pmc_dict_train_host: every pointer is host memory; the call is synchronous, takes the context's host lock,
+ * restores the caller's current HIP device, and also returns PMC_E_ARG when the truncated sample bytes sum to more
+ * than 256 MiB (that is a training sample, not a workload).
+ * WRITES: dict[0 .. 64 m) and *dict_len = 64 m, and nothing else: bytes [64 m, dict_size) of dict are not written.
+ * PMC_E_ARG, with no device touched: a NULL context, n == 0, n > PMC_DICT_TRAIN_MAX_SAMPLES, a dict_size that is
+ * not a multiple of 64 in [64, 8192], or a NULL array.
+ * Neither call sets the dictionary: the caller passes the bytes to pmc_ctx_set_dictionary or writes them to the
+ * file that PMC_DICT names.  A result of 0 bytes, or one whose CRC-32 is 0, is refused by pmc_ctx_set_dictionary
+ * as ever.
+ * Scratch: the table (4 MiB), one 16-byte slot per block of an epoch's score launch and E rows of 64 bytes --
+ * under 4.2 MiB whatever the samples are (csrc/pmc_plan.hpp plan_dict_train); the context keeps it until
+ * pmc_ctx_destroy.  The launches are not part of pmc_ctx_kernel_times.
+ *
+ * Not provided: training from a store's extents; group, slab and server wrappers; rotation of several live
+ * dictionaries; parameters other than the fixed d, K, F; sample weighting. */
+#define PMC_DICT_TRAIN_MAX_SAMPLES 262144
+int pmc_dict_train_batch(pmc_ctx *ctx, const uint8_t *src, const uint64_t *src_off, const uint32_t *src_len,
+                         uint32_t n, uint32_t dict_size, uint8_t *dict, uint32_t *dict_len, void *stream);
+int pmc_dict_train_host(pmc_ctx *ctx, const uint8_t *src, const uint64_t *src_off, const uint32_t *src_len,
+                        uint32_t n, uint32_t dict_size, uint8_t *dict, uint32_t *dict_len);
+
 void pmc_ctx_destroy(pmc_ctx *ctx);
 /* Default context (device 0), created on first use; used by the drop-in. */
 pmc_ctx *pmc_default_ctx(void);

@@ -203,6 +203,9 @@ struct pmc_ctx {
     // length and id (CRC-32; 0 = none).  Written with host_mu and both dir_mu held, read under a dir_mu.
     DevBuf dict;
     uint32_t dict_len = 0, dict_id = 0;
+    // dictionary training (pmc_dict_train.hip): the table, block slots and rows (pmc_plan.hpp DictTrainPlan); a
+    // compress-direction scratch
+    DevBuf train;
     // host-call routing (pmc_ctx_path_counts): [0] / [1] compress / decompress calls on the latency
     // path, [2] / [3] on the throughput pipeline
     uint64_t path_calls[4] = {0, 0, 0, 0};
@@ -719,6 +722,7 @@ PMC_API void pmc_ctx_destroy(pmc_ctx *c) {
     c->pat.release();
     c->patr.release();
     c->dict.release();
+    c->train.release();
     c->guard.release();
     c->rlist.release();
     c->lvsel.release();

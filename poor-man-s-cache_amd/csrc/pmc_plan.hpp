@@ -1039,4 +1039,46 @@ struct PinnedSlot {
     uint64_t need = c.meta;
 };
 
+// ---- dictionary training (pmc_dict_train.hip; include/pmc_codec.h "dictionary training") ---------------------
+constexpr uint32_t kTrainKmer = 8, kTrainSeg = 64, kTrainBits = 20; // d, K, F
+constexpr uint32_t kTrainWin = kTrainSeg - kTrainKmer + 1;          // W = 57 positions per segment
+constexpr uint64_t kTrainMult = 0x9E3779B185EBCA87ull;
+constexpr uint32_t kTrainSlotBytes = 16;   // a block's best: u64 score, u32 sample, u32 start
+constexpr uint32_t kTrainWavesPerCu = 16;  // one-wave blocks of the count and score kernels per CU
+constexpr uint64_t kTrainHostBytes = 256ull << 20; // pmc_dict_train_host: the most sample bytes of a call
+
+inline bool dict_train_args_ok(uint64_t n, uint64_t dict_size) {
+    return n >= 1 && n <= PMC_DICT_TRAIN_MAX_SAMPLES && dict_size >= kTrainSeg && dict_size <= PMC_DICT_MAX &&
+           dict_size % kTrainSeg == 0;
+}
+
+// A training call over n samples for a dictionary of dict_size bytes (dict_train_args_ok).  E epochs; epoch e owns
+// the samples [lo(e), hi(e)), one wave per sample up to the resident waves, and every block of its score launch
+// writes one slot, so max_blocks slots serve every epoch.  Scratch: the table (2^F u32), the count of selected
+// segments (u32, in a 256-byte row of its own), the slots, E rows of 64 bytes.  At most 4 MiB + 256 + 16 *
+// kTrainWavesPerCu * cus + 8 KiB bytes, whatever the samples are.
+struct DictTrainPlan {
+    uint32_t E;
+    uint32_t n;
+    uint32_t count_blocks, max_blocks;
+    uint64_t table, nsel, slots, rows, bytes; // offsets into the scratch; its size
+    uint32_t lo(uint32_t e) const { return (uint32_t)((uint64_t)e * n / E); }
+    uint32_t hi(uint32_t e) const { return (uint32_t)(((uint64_t)e + 1) * n / E); }
+    uint32_t blocks(uint32_t e) const { return std::min<uint32_t>(hi(e) - lo(e), max_blocks); } // 0: nothing to launch
+};
+inline DictTrainPlan plan_dict_train(uint32_t n, uint32_t dict_size, uint64_t cus) {
+    DictTrainPlan P{};
+    P.E = dict_size / kTrainSeg;
+    P.n = n;
+    const uint64_t resident = std::max<uint64_t>(1, cus) * kTrainWavesPerCu;
+    P.count_blocks = (uint32_t)std::min<uint64_t>(n, resident);
+    P.max_blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n + P.E - 1) / P.E, resident);
+    P.table = 0;
+    P.nsel = P.table + (4ull << kTrainBits);
+    P.slots = P.nsel + 256;
+    P.rows = (P.slots + (uint64_t)kTrainSlotBytes * P.max_blocks + 255) & ~(uint64_t)255;
+    P.bytes = P.rows + (uint64_t)P.E * kTrainSeg;
+    return P;
+}
+
 } // namespace pmc

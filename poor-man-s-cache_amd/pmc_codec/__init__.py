@@ -100,6 +100,8 @@ SIGNATURES = {
     "pmc_ctx_set_dictionary": (_c.c_int, [_p, _c.c_char_p, _c.c_size_t]),
     "pmc_ctx_get_dictionary_id": (_c.c_int, [_p, _c.POINTER(_u32)]),
     "pmc_group_set_dictionary": (_c.c_int, [_p, _c.c_char_p, _c.c_size_t]),
+    "pmc_dict_train_batch": (_c.c_int, [_p, _p, _p, _p, _u32, _u32, _p, _p, _p]),
+    "pmc_dict_train_host": (_c.c_int, [_p, _p, _p, _p, _u32, _u32, _p, _p]),
     "pmc_ctx_set_index": (_c.c_int, [_p, _c.c_int]),
     "pmc_ctx_get_index": (_c.c_int, [_p, _c.POINTER(_c.c_int)]),
     "pmc_group_set_index": (_c.c_int, [_p, _c.c_int]),
@@ -497,6 +499,35 @@ class Context:
                                             _ptr(dst_off), _ptr(dst_cap), _ptr(dst_len), _ptr(rc), stream)
         if r != 0:
             raise CodecUnavailable(f"pmc_gzip_grow_range_batch = {r}: {last_error()}")
+
+    def train_dictionary(self, values, size=2048) -> bytes:
+        """A dictionary of at most `size` bytes (a multiple of 64 in 64 .. 8192) trained on the GPU from the sample
+        values, a list of bytes (include/pmc_codec.h "dictionary training").  Deterministic; it may be shorter than
+        `size`, even empty.  It is not set: pass it to set_dictionary, or write it to the file PMC_DICT names."""
+        import numpy as np
+        n = len(values)
+        src = b"".join(values)
+        src_len = np.fromiter(map(len, values), dtype=np.uint32, count=n)
+        src_off = np.zeros(max(n, 1), dtype=np.uint64)
+        src_off[1:n] = np.cumsum(src_len[:-1], dtype=np.uint64)
+        out = np.zeros(DICT_MAX, dtype=np.uint8)
+        out_len = _u32(0)
+        r = lib().pmc_dict_train_host(self.handle, src, src_off.ctypes.data, src_len.ctypes.data, n, size,
+                                      out.ctypes.data, ctypes.byref(out_len))
+        if r == E_ARG:
+            raise ValueError(f"pmc_dict_train_host({n} samples, {len(src)} bytes, size {size}) = {r}")
+        if r != 0:
+            raise CodecUnavailable(f"pmc_dict_train_host = {r}: {last_error()}")
+        return out[:out_len.value].tobytes()
+
+    def train_dictionary_device(self, src, src_off, src_len, size, dict, dict_len, stream=0):
+        """train_dictionary on device tensors: dict (at least `size` bytes) receives the dictionary and dict_len
+        (one uint32) its length; bytes of dict behind that length are not written.  Enqueue only, ordered with
+        this context's compress calls."""
+        r = lib().pmc_dict_train_batch(self.handle, _ptr(src), _ptr(src_off), _ptr(src_len), _n(src_len), size,
+                                       _ptr(dict), _ptr(dict_len), stream)
+        if r != 0:
+            raise CodecUnavailable(f"pmc_dict_train_batch = {r}: {last_error()}")
 
     def rewrite_counts(self):
         """{served, declined, decoded, compressed, copied}: rewrite requests answered OK / answered E_NO_INDEX, and
