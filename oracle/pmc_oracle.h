@@ -78,14 +78,14 @@ typedef struct {
 size_t oracle_get_block_facts(oracle_block_facts *out, size_t cap);
 
 /* Search log: what the last oracle_gzip_compress_dp call (a value of at most ORACLE_LOG_MAX bytes; longer values
- * leave an empty log) did, for tests/front_values.py.  One oracle_search_rec per longest_match call of the lazy
+ * leave an empty log; the buffers are allocated by the value's length) did, for tests/front_values.py.  One oracle_search_rec per longest_match call of the lazy
  * parse: the position, prev_length, the candidates examined, the winner (the longest candidate, nearest first:
  * win_ord is its 0-based place in the chain, 0xFFFFFFFF with no candidate; win_len may be <= prev_length, in which
  * case the parse ignores it), first_len the nearest candidate's common prefix (capped at nice), how the walk
  * ended, and whether a candidate of the same hash and other leading bytes was examined.  One oracle_token_rec per
  * symbol: len 0 is a literal whose byte is dist.  Both return the number of records of the call and write the
  * first min(cap, records). */
-#define ORACLE_LOG_MAX 65536
+#define ORACLE_LOG_MAX (1u << 20)
 enum { ORACLE_END_HASH = 0,  /* the entry below the chain has another hash */
        ORACLE_END_START,     /* the chain reached the start of the sorted array */
        ORACLE_END_NIL,       /* ... position 0 (or the window base), which zlib reads as NIL */
@@ -117,11 +117,40 @@ size_t oracle_chain_counts(const uint8_t *in, size_t len, uint32_t *cnt, size_t 
  *   FIRST_K       candidates from ordinal arg on are ignored
  *   SKIP_K        exactly the candidate of ordinal arg is ignored (it still counts towards the cap)
  *   NICE_258      nice stays 258 near the end of the value: the compare runs on into the zeros past it, the
- *                 winner is picked by that length and the result clipped to the bytes left */
+ *                 winner is picked by that length and the result clipped to the bytes left
+ * Rules only values above one window meet (tests/large_conf_values.py):
+ *   MAXDIST_FIRST_LT     the first candidate needs d < MAX_DIST (zlib: d <= MAX_DIST)
+ *   MAXDIST_FIRST_32507  the first candidate may lie at d <= MAX_DIST + 1
+ *   MAXDIST_LATER_LE     later candidates may lie at d <= MAX_DIST (zlib: d < MAX_DIST)
+ *   MAXDIST_LATER_32505  later candidates need d < MAX_DIST - 1
+ *   MAX_LAZY_OFF         the search also runs at prev_length == 258
+ *   STORED_ANY           tr_flush_block always gets the block's bytes: the window base never forbids a stored block
+ *   SLIDE_EARLY          the window base moves when i - B >= W_SIZE + MAX_DIST - 1
+ *   SLIDE_LATE           ... when i - B >= W_SIZE + MAX_DIST + 1
+ *   SLIDE_NIL_OFF        a candidate at or below the window base is NIL only while the base is 0 */
 enum { ORACLE_RULE_ZLIB = 0, ORACLE_RULE_TOO_FAR_GE, ORACLE_RULE_TOO_FAR_4097, ORACLE_RULE_CHAIN_NOCAP,
        ORACLE_RULE_GOOD_OFF, ORACLE_RULE_GOOD_33, ORACLE_RULE_TIE_FAR, ORACLE_RULE_NIL_OK, ORACLE_RULE_LAZY_LT,
-       ORACLE_RULE_COLLIDE_FREE, ORACLE_RULE_FIRST_K, ORACLE_RULE_SKIP_K, ORACLE_RULE_NICE_258, ORACLE_RULE_CAP4096_OFF, ORACLE_RULE_LAZY_GE };
+       ORACLE_RULE_COLLIDE_FREE, ORACLE_RULE_FIRST_K, ORACLE_RULE_SKIP_K, ORACLE_RULE_NICE_258, ORACLE_RULE_CAP4096_OFF, ORACLE_RULE_LAZY_GE,
+       ORACLE_RULE_MAXDIST_FIRST_LT, ORACLE_RULE_MAXDIST_FIRST_32507, ORACLE_RULE_MAXDIST_LATER_LE,
+       ORACLE_RULE_MAXDIST_LATER_32505, ORACLE_RULE_MAX_LAZY_OFF, ORACLE_RULE_STORED_ANY, ORACLE_RULE_SLIDE_EARLY,
+       ORACLE_RULE_SLIDE_LATE, ORACLE_RULE_SLIDE_NIL_OFF };
 size_t oracle_compress_variant(int rule, unsigned arg, const uint8_t *in, size_t len, uint8_t *out);
+
+/* The window base (fill_window's slides so far) at a loop top t of a value of len bytes, as a closed form of t
+ * alone; oracle_base_diffs: the loop tops of the last oracle_gzip_compress_dp call at which the base it keeps step
+ * by step was another (0 unless the closed form is wrong). */
+size_t oracle_window_base(size_t t, size_t len);
+uint64_t oracle_base_diffs(void);
+
+/* The speculative parse of the large-value pipeline (csrc/pmc_deflate_large.hip, lv_parse_kernel), stated by the
+ * oracle: deflate_slow from a fresh state at `start`, chains over the whole value, up to the first loop top at or
+ * past `stop` (stop == len: with deflate_slow's trailing literal).  One oracle_state_rec per loop top at which
+ * match_length == 2, so that no match is pending: code 1 with no literal pending, 2 with one, and the tokens
+ * emitted so far.  Writes the first min(cap_s, states) states and min(cap_t, tokens) tokens, *ntok receives the
+ * token count; returns the number of states.  Leaves the logs of the last compress call alone. */
+typedef struct { uint32_t pos, code, ntok; } oracle_state_rec;
+size_t oracle_parse_from(const uint8_t *in, size_t len, size_t start, size_t stop, oracle_state_rec *st, size_t cap_s,
+                         oracle_token_rec *tk, size_t cap_t, size_t *ntok);
 
 /* splitmix64-based synthetic value generator shared with the GPU generator
  * (SURVEY.md §8d): value i of size V is corpus[off_i : off_i+V],

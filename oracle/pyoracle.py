@@ -131,14 +131,16 @@ def last_block_facts():
 
 
 # ---- search facts and rule variants (pmc_oracle.h) -----------------------------------------------------------
-LOG_MAX = 65536
+LOG_MAX = 1 << 20
 END_HASH, END_START, END_NIL, END_CAP4096, END_CAP1024, END_NICE, END_DIST = range(7)
 SEARCH_DTYPE = np.dtype([(k, "<u4") for k in ("pos", "prev_length", "examined", "win_ord", "win_len", "win_dist",
                                                "first_len", "end", "collide")])
 TOKEN_DTYPE = np.dtype([(k, "<u4") for k in ("pos", "len", "dist")])
 RULES = {name: k + 1 for k, name in enumerate((
     "too_far_ge", "too_far_4097", "chain_nocap", "good_off", "good_33", "tie_far", "nil_ok", "lazy_lt",
-    "collide_free", "first_k", "skip_k", "nice_258", "cap4096_off", "lazy_ge"))}
+    "collide_free", "first_k", "skip_k", "nice_258", "cap4096_off", "lazy_ge",
+    "maxdist_first_lt", "maxdist_first_32507", "maxdist_later_le", "maxdist_later_32505", "max_lazy_off", "stored_any",
+    "slide_early", "slide_late", "slide_nil_off"))}
 
 
 def _log(fn, dtype):
@@ -176,6 +178,40 @@ def compress_variant(rule: str, arg: int, data: bytes) -> bytes:
     out = ctypes.create_string_buffer(L.oracle_gzip_bound(len(data)))
     n = L.oracle_compress_variant(RULES[rule], arg, data, len(data), out)
     return out.raw[:n]
+
+
+STATE_DTYPE = np.dtype([(k, "<u4") for k in ("pos", "code", "ntok")])
+
+
+def parse_from(data: bytes, start: int, stop: int):
+    """(states, tokens) of deflate_slow from a fresh state at `start` up to the first loop top at or past `stop`
+    (pmc_oracle.h: oracle_parse_from), as structured arrays (STATE_DTYPE, TOKEN_DTYPE)."""
+    L = lib()
+    L.oracle_parse_from.restype = ctypes.c_size_t
+    L.oracle_parse_from.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p,
+                                    ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+    cap = max(min(stop, len(data)) - start, 0) + 2
+    st, tk = np.zeros(cap, STATE_DTYPE), np.zeros(cap, TOKEN_DTYPE)
+    nt = ctypes.c_size_t(0)
+    ns = L.oracle_parse_from(data, len(data), start, stop, st.ctypes.data_as(ctypes.c_void_p), cap,
+                             tk.ctypes.data_as(ctypes.c_void_p), cap, ctypes.byref(nt))
+    assert ns <= cap and nt.value <= cap
+    return st[:ns], tk[:nt.value]
+
+
+def window_base(t: int, n: int) -> int:
+    """The window base at a loop top t of a value of n bytes (pmc_oracle.h: oracle_window_base)."""
+    L = lib()
+    L.oracle_window_base.restype = ctypes.c_size_t
+    L.oracle_window_base.argtypes = [ctypes.c_size_t, ctypes.c_size_t]
+    return L.oracle_window_base(t, n)
+
+
+def base_diffs() -> int:
+    """Loop tops of the last compress(dp=True) whose step-by-step window base was not window_base()."""
+    L = lib()
+    L.oracle_base_diffs.restype = ctypes.c_uint64
+    return L.oracle_base_diffs()
 
 
 def gen_values(corpus: bytes, seed: int, kind: int, first: int, n: int, vlen: int) -> np.ndarray:

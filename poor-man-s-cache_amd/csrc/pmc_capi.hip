@@ -824,6 +824,16 @@ static InflateKernel wave_kernel(bool hbm, bool dict) {
 // fast (PMC_LEVEL_FAST_ALL): no sort, rank, map or stitch scratch -- one wave per segment parses it in LDS.
 // Either way the large-value emit kernel then writes the members (header byte 8 = 2 / 4).
 // The loop body depends on the round only through its plan.
+// A round's tables and scratch fit 24 GiB (PMC_LV_ROUND_MB lowers or raises that, for tests: a budget of a few
+// values' cost cuts a small batch into several rounds; a value above the budget is a round of its own).
+static uint64_t lv_round_budget() {
+    static const uint64_t budget = [] {
+        const char *e = getenv("PMC_LV_ROUND_MB");
+        const long long mb = e ? atoll(e) : 0;
+        return mb > 0 && mb < (1ll << 24) ? (uint64_t)mb << 20 : 24ull << 30; // (unset, not a number, <= 0: the default)
+    }();
+    return budget;
+}
 static int large_values(pmc_ctx *ctx, const DeflateArgs &a, uint64_t lo, uint64_t hi, bool fast, hipStream_t st) {
     const uint64_t n = a.n;
     int r = ctx->lvsel.ensure(8 + 8 * n);
@@ -841,7 +851,7 @@ static int large_values(pmc_ctx *ctx, const DeflateArgs &a, uint64_t lo, uint64_
     std::vector<std::pair<uint32_t, uint32_t>> vals(cnt);
     for (uint32_t k = 0; k < cnt; k++) vals[k] = {list[2 * k], list[2 * k + 1]};
     std::sort(vals.begin(), vals.end());
-    const uint64_t budget = 24ull << 30;
+    const uint64_t budget = lv_round_budget();
     // (the index switch acts on the segmented fast members only; read once per call)
     const uint32_t idx_chunk = fast && ctx->index ? kIdxChunk : 0u;
     const uint32_t idx_crc = idx_chunk && ctx->index_crc ? 1u : 0u;

@@ -11,9 +11,12 @@
 //     rank array R (R[S[k]] = k) and HC[x] = zlib would search at x (the nearest same-hash earlier
 //     position exists, is not NIL position 0 and lies within MAX_DIST).  zlib's chain of x is then the
 //     run S[R[x] - 1], S[R[x] - 2], ... of equal hash, cut at MAX_DIST (deflate_dp.c restates this).
-//     Window slides never change a match: after the first slide every search position lies more than
-//     MAX_DIST past the window base, so the base's NIL only ever hides candidates the distance limit
-//     hides anyway.
+//     Window slides change a match at one kind of position only: after a slide every search position lies
+//     more than MAX_DIST past the window base, so the base's NIL hides only candidates the distance limit
+//     hides anyway -- except at the loop top that slides with the base exactly
+//     32768 + MAX_DIST behind, which only the last MIN_LOOKAHEAD - 1 positions of a value can be (earlier,
+//     fill_window waits one position longer).  There the new base is the candidate at MAX_DIST, and NIL:
+//     lv_rank_kernel gives such a position no search (tests/large_conf_values.py: v:slide_nil_off).
 //  2. parse (lv_parse_kernel): one wave per segment runs deflate_slow from a fresh state at the
 //     segment start over global memory, longest_match 64 chain candidates per step (lane per
 //     candidate, nearest wins ties), and on through kLvOverlap positions of the next segment.  At each
@@ -35,6 +38,7 @@
 namespace pmc {
 
 constexpr uint32_t kLvMaxDist = 32768 - 262, kLvTooFar = 4096;
+constexpr uint32_t kLvSlideAt = 32768 + kLvMaxDist; // fill_window slides at a loop top this far past the base
 
 __device__ __forceinline__ uint32_t lv_hash(uint32_t w) {
     return ((w & 0xff) << 10 ^ ((w >> 8) & 0xff) << 5 ^ ((w >> 16) & 0xff)) & 0x7fffu;
@@ -214,7 +218,12 @@ __global__ void __launch_bounds__(256) lv_rank_kernel(LargeArgs a) {
                 a.R[k.pb + p] = x;
                 uint32_t cnt = x - rs;
                 if (cnt && a.S[k.pb + rs] == 0) cnt--; // (NIL heads its run)
-                const bool search = x > 0 && h == hp && qp != 0 && p - qp <= kLvMaxDist;
+                // (the window base is NIL too: it is the candidate at MAX_DIST exactly, at the one loop top where
+                // fill_window slides with the base that far behind -- p = 65274 + 32768 k with the value's end
+                // nearer than MIN_LOOKAHEAD; everywhere else the base lies beyond MAX_DIST)
+                const bool at_base = p - qp == kLvMaxDist && p >= kLvSlideAt && ((p - kLvSlideAt) & 32767u) == 0 &&
+                                     B.len - p < 262u;
+                const bool search = x > 0 && h == hp && qp != 0 && p - qp <= kLvMaxDist && !at_base;
                 a.HC[k.pb + p] = (uint8_t)(search ? (cnt < 255 ? cnt : 255) : 0);
             }
             ph = readlane(h, 63);
